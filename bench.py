@@ -11,6 +11,16 @@ inversion count 2 N^3 and is the whole-job aggregate (strong s
     python bench.py [--gpus N] [--steps K] [--warmup W]            # starts its own N rank processes
     torchrun --nproc-per-node N bench.py --gpus N --steps K ...    # or one rank per process from torchrun
 
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps,
+writes its outputs if ``--dump-outputs DIR`` is given, and prints the JSON line.  ``--full`` adds
+everything else the record can carry: the residual gate on the last timed solve, RCCL's transport
+report, and at p > 1 the extra untimed profiled solve (phase breakdown, per-collective bandwidth).
+
+``--dump-outputs DIR``: after the timed steps, what the last one computed -- the inverse as a caller
+of the engine would download it -- goes to DIR as float arrays (``dump_outputs`` below).  The input
+is a function of ``--gen``, ``--seed``, ``--size`` and ``--dtype`` alone, so two builds run with the
+same arguments can be compared output for output.
+
 Process model (the reference's SPMD start, main.cpp:65-74): one process per GPU.  Without
 torchrun's environment, ``--gpus N > 1`` makes this process a launcher that never touches a GPU: it
 starts N copies of itself with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, forwards rank 0's
@@ -20,10 +30,11 @@ every collective of the solve is RCCL, issued by the native engine from C++.
 
 Failure handling: every host wait of the engine is bounded by ``--comm-timeout`` (default 90 s,
 below the driver's 600 s), so a hung peer turns into a non-zero exit on every rank, each naming
-its step, phase and the collective it sat in.  A wrong inverse is a failure too: after the timed
-loop the residual ||A A^-1 - I||_inf (the reference's check, main.cpp:490-507) is normalised by
-||A|| ||A^-1|| eps and gated at 2n (``utils.metrics``, LAPACK's inverse test ratio); non-finite or
-above the gate, the JSON line says ``"check": "residual_failed"`` and every rank exits 2.
+its step, phase and the collective it sat in.  With ``--full`` a wrong inverse is a failure too:
+after the timed loop the residual ||A A^-1 - I||_inf (the reference's check, main.cpp:490-507) is
+normalised by ||A|| ||A^-1|| eps and gated at 2n (``utils.metrics``, LAPACK's inverse test ratio);
+non-finite or above the gate, the JSON line says ``"check": "residual_failed"`` and every rank
+exits 2.  A plain run reports ``"check": "skipped"``.
 
 ``--same-gpu`` (rehearsal on a one-GPU box): all ranks share device 0 and RCCL is told that every
 rank is its own host (``NCCL_HOSTID``), so it accepts the duplicate device and connects the ranks
@@ -63,6 +74,12 @@ def parse_args(argv=None):
     ap.add_argument("--depth", type=int, default=0,
                     help="elimination steps fused per trailing update (0 = the engine's choice)")
     ap.add_argument("--no-residual", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the residual gate on the last timed solve, "
+                         "RCCL's transport report, at p > 1 the extra untimed profiled solve")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy "
+                         "(a fixed seeded sample of the inverse's rows and columns, at most 64 MB)")
     ap.add_argument("--pivot", choices=["block-min-inv-norm", "partial"], default="block-min-inv-norm",
                     help="pivot rule: the reference's smallest ||inv(block)|| (the benchmarked algorithm) "
                          "or block partial pivoting (a faster alternative mode)")
@@ -174,6 +191,58 @@ def _merge_transports(per_rank):
     return out
 
 
+DUMP_BYTES = 24 << 20  # per sampled array of --dump-outputs (rows and columns: 48 MiB of the 64 MB)
+
+
+def dump_outputs(eng, args, rank, world, gpu, out_dir):
+    """The result of the engine's last solve, as DIR/<name>.npy in the engine's precision (collective).
+
+    inverse_rows.npy  (k, n)  rows sample_rows of inv(A), global row order
+    inverse_cols.npy  (n, k)  columns sample_cols of inv(A), global row order
+    sample_rows.npy, sample_cols.npy  (k,)  the sampled global indices (float64)
+
+    k = min(n, 24 MiB / one fp64 row): everything up to n = 1773, 96 rows and 96 columns at
+    n = 32768.  The indices are drawn by a generator seeded with --seed, so the same arguments give
+    the same sample.  Every rank copies its rows out device-to-device (the path a caller holding a
+    device tensor takes, Engine::download_rows_device) and takes its share; rank 0 assembles."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    from mpi_jordan_crazy_acceleration_amd.parallel.layout import global_rows
+
+    n = args.n
+    k = min(n, max(1, DUMP_BYTES // (8 * n)))
+    rng = np.random.default_rng(args.seed)
+    rows = np.sort(rng.choice(n, size=k, replace=False))
+    cols = np.sort(rng.choice(n, size=k, replace=False))
+    mine = global_rows(n, args.m, world, rank)  # global index of every local row, in storage order
+    assert len(mine) == eng.layout["real_rows"]
+    local = torch.empty((len(mine), n), dtype=torch.float64 if args.dtype == "fp64" else torch.float32,
+                        device="cuda" if gpu else "cpu")
+    if len(mine):
+        eng.download_rows_device(local.data_ptr(), n)
+    pick = np.flatnonzero(np.isin(mine, rows))
+    part = {"row_ids": mine[pick], "rows": local[torch.as_tensor(pick, device=local.device)].cpu().numpy(),
+            "col_ids": mine, "cols": local[:, torch.as_tensor(cols, device=local.device)].cpu().numpy()}
+    del local
+    parts = [part]
+    if dist.is_initialized():
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object(part, parts, dst=0)
+    if rank != 0:
+        return
+    inv_rows = np.empty((k, n), dtype=part["rows"].dtype)
+    inv_cols = np.empty((n, k), dtype=part["cols"].dtype)
+    for p in parts:
+        inv_rows[np.searchsorted(rows, p["row_ids"])] = p["rows"]
+        inv_cols[p["col_ids"]] = p["cols"]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("inverse_rows", inv_rows), ("inverse_cols", inv_cols),
+                    ("sample_rows", rows.astype(np.float64)), ("sample_cols", cols.astype(np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ----------------------------------------------------------------------------- one rank
 def run_rank(args) -> int:
     gpu = args.device == "gpu"
@@ -200,7 +269,7 @@ def run_rank(args) -> int:
     # which transport RCCL connects the ranks with (P2P over xGMI, or sockets): its INFO log of the
     # connection setup goes to a per-rank file, parsed after the warm-up (utils/rccl_log.py)
     rccl_log = None
-    if gpu and (world > 1 or args.force_rccl):
+    if args.full and gpu and (world > 1 or args.force_rccl):
         import tempfile
 
         from mpi_jordan_crazy_acceleration_amd.utils import rccl_log as _rl
@@ -281,12 +350,14 @@ def run_rank(args) -> int:
         rhs_b = (np.ones(args.n) if args.rhs == "ones" else
                  np.random.default_rng(args.seed + 1).uniform(-1.0, 1.0, args.n))
     rhs_info = {}
+    rhs_x = []
 
     def step():
         eng.generate(args.gen, args.seed)
         st = eng.solve()
         if rhs_b is not None and st["status"] == 0:  # the refined solve is part of the timed step
-            _, info = eng.solve_rhs_generated(args.gen, args.seed, rhs_b, args.refine)
+            x, info = eng.solve_rhs_generated(args.gen, args.seed, rhs_b, args.refine)
+            rhs_x[:] = [x]
             rhs_info.clear()
             rhs_info.update(info)
         return st
@@ -313,11 +384,23 @@ def run_rank(args) -> int:
     except RuntimeError as e:
         return fail(e)
     st = stats[-1] if stats else {"status": 0, "offdiag_pivots": 0, "host_wait_ms": 0.0, "seconds": 0.0}
+    if args.dump_outputs and st["status"] == 0:
+        if args.steps + args.warmup == 0:
+            return fail("--dump-outputs needs at least one step")
+        try:  # before anything below touches the engine again: this is the last timed step's result
+            dump_outputs(eng, args, rank, world, gpu, args.dump_outputs)
+            if rhs_x and rank == 0:
+                import numpy as np
+
+                np.save(os.path.join(args.dump_outputs, "x.npy"), np.asarray(rhs_x[0], dtype=np.float64))
+        except RuntimeError as e:
+            return fail(e)
     # The gate checks the LAST TIMED solve (its output is still in the engine): the profiled solve
     # below runs another schedule, so a race of the unprofiled one must fail here.
     res = None
     norm_a = norm_inv = None
-    if not args.no_residual and st["status"] == 0:
+    residual = args.full and not args.no_residual
+    if residual and st["status"] == 0:
         try:
             norm_a = eng.input_norm_inf()
             norm_inv = eng.result_norm_inf()
@@ -328,7 +411,7 @@ def run_rank(args) -> int:
         # p > 1: one extra UNTIMED solve with the per-phase device timers, so a multi-GPU record
         # carries its own phase breakdown and host waits (the timed steps stay unprofiled)
         prof = None
-        if world > 1 and not args.profile:
+        if args.full and world > 1 and not args.profile:
             eng.set_profile(True)
             prof = step()
             eng.set_profile(False)
@@ -364,7 +447,7 @@ def run_rank(args) -> int:
                                                                   residual_ratio)
 
     bound = rho = None
-    if args.no_residual:
+    if not residual:
         check = "skipped"
     else:
         bound = residual_bound(args.n, norm_a or 0.0, norm_inv or 0.0, args.dtype)

@@ -2,8 +2,8 @@
 residual gate that decides whether a benchmarked inverse is correct.
 
 The reference prints ``residual: ||A A^-1 - I||_inf`` after every run (main.cpp:490-507) but never
-fails on it.  Here a wrong inverse must be a failure, not a fast success: ``bench.py`` exits 2 when
-the residual is non-finite or fails the gate below (the CLI's ``--check-residual TOL`` is the
+fails on it.  Here a wrong inverse must be a failure, not a fast success: ``bench.py --full`` exits
+2 when the residual is non-finite or fails the gate below (the CLI's ``--check-residual TOL`` is the
 absolute form).
 
 The gate is on the NORMALISED residual (LAPACK's inverse test ratio, xGET03)

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Policy-cliff sweep: for each N, the engine's auto policy against its
 neighbours -- CU reservation flipped (0 <-> 32), depth flipped (2 <-> 4), and the skip_cols / lat_reg
-pair flipped -- on one GPU, fp64, m = 128, each a `bench.py` run (subprocess) with the override in
-its environment.  Writes one JSON line per run to OUT and prints a markdown table.
+pair flipped -- on one GPU, fp64, m = 128, each a `bench.py --full` run (subprocess, residual gate
+on) with the override in its environment.  Writes one JSON line per run to OUT and prints a markdown table.
 
     python3 scripts/policy_sweep.py OUT.jsonl [--sizes 6144,12288,20480,24576,40960] [--steps 5 --warmup 2]
 """
@@ -19,8 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run(n, env_extra, steps, warmup, timeout):
     env = dict(os.environ, **env_extra)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", str(n), "--steps", str(steps),
-                        "--warmup", str(warmup)], env=env, capture_output=True, text=True, timeout=timeout)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--size", str(n), "--steps",
+                        str(steps), "--warmup", str(warmup)], env=env, capture_output=True, text=True,
+                       timeout=timeout)
     if r.returncode != 0:
         raise SystemExit(f"bench.py N={n} {env_extra} failed rc={r.returncode}: {r.stderr[-1500:]}")
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -50,7 +51,7 @@ def main():
                 if name == "auto":
                     d = base
                 elif name.startswith("depth"):
-                    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--size", str(n),
+                    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--size", str(n),
                                         "--steps", str(a.steps), "--warmup", str(a.warmup), "--depth",
                                         name.split()[1]], capture_output=True, text=True, timeout=a.timeout)
                     if r.returncode != 0:

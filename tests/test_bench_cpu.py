@@ -27,7 +27,7 @@ def _torchrun(nproc, *args, env_extra=None, timeout=240):
     env.setdefault("OMP_NUM_THREADS", "1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--device", "cpu", *args]
+           os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--device", "cpu", "--full", *args]
     return subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=timeout)
 
 
@@ -59,7 +59,7 @@ def _ranks(world, *args, env_extra=None, timeout=180):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), LOCAL_WORLD_SIZE=str(world),
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=port, OMP_NUM_THREADS="1", **(env_extra or {}))
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world),
-                                       "--device", "cpu", *args], cwd="/tmp", env=env,
+                                       "--device", "cpu", "--full", *args], cwd="/tmp", env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     out = []
     try:
@@ -88,13 +88,15 @@ def test_bench_alloc_failure_on_one_rank(stage, status):
             assert f"status {status}" in e
 
 
-def _self_launch(nproc, *args, env_extra=None, timeout=240):
-    """`python bench.py --gpus N` with no torchrun environment: bench.py starts its own ranks."""
+def _self_launch(nproc, *args, env_extra=None, timeout=240, full=True):
+    """`python bench.py --gpus N` with no torchrun environment: bench.py starts its own ranks.
+    full: with `--full` (the residual gate, the profiled solve), as every test here but the plain one."""
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(env_extra or {})
     env.setdefault("OMP_NUM_THREADS", "1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--device", "cpu", *args]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--device", "cpu",
+           *(["--full"] if full else []), *args]
     return subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=timeout)
 
 
@@ -120,6 +122,84 @@ def test_bench_self_launch_matches_torchrun():
         assert r["pivot_rows"]["bytes"] > 0 and r["pivot_records"]["calls"] > 0
         assert r["pivot_rows"]["GB_s"] is None or r["pivot_rows"]["GB_s"] > 0
     assert len(da["step_ms"]) == 2
+
+
+def _check_dump(out, n, k, seed):
+    """The files of `--dump-outputs`: k sampled rows and k sampled columns of inv(A), consistent with
+    each other, against A regenerated on the host (rows of inv(A) times A and A times columns of
+    inv(A) are rows and columns of I; 1e-8 is the bound of the residual tests above)."""
+    import numpy as np
+
+    from mpi_jordan_crazy_acceleration_amd.utils import generate_matrix
+
+    assert set(out) == {"inverse_rows.npy", "inverse_cols.npy", "sample_rows.npy", "sample_cols.npy"}
+    assert all(v.dtype == np.float64 for v in out.values())
+    assert sum(v.nbytes for v in out.values()) <= 64e6
+    rows, cols = out["sample_rows.npy"].astype(int), out["sample_cols.npy"].astype(int)
+    assert len(rows) == len(cols) == k and len(set(rows)) == k and len(set(cols)) == k
+    assert rows.min() >= 0 and rows.max() < n and cols.min() >= 0 and cols.max() < n
+    inv_rows, inv_cols = out["inverse_rows.npy"], out["inverse_cols.npy"]
+    assert inv_rows.shape == (k, n) and inv_cols.shape == (n, k)
+    A = generate_matrix(n, "random", seed)
+    eye = np.eye(n)
+    assert np.abs(inv_rows @ A - eye[rows]).max() < 1e-8
+    assert np.abs(A @ inv_cols - eye[:, cols]).max() < 1e-8
+    assert np.array_equal(inv_rows[:, cols], inv_cols[rows])
+
+
+def test_bench_plain_run_dumps_the_inverse(tmp_path, nproc=3, n=203, m=8):
+    """A plain run (no `--full`): the headline fields, no residual gate, no profiled solve; and
+    `--dump-outputs` writes the last timed step's inverse (all of it at this size) in global row
+    order at any p, the same from run to run."""
+    import numpy as np
+
+    args = ("--steps", "2", "--warmup", "1", "--size", str(n), "--block", str(m), "--seed", "11")
+    runs = []
+    for d in ("a", "b"):
+        r = _self_launch(nproc, *args, "--dump-outputs", str(tmp_path / d), full=False)
+        assert r.returncode == 0, r.stderr[-3000:]
+        runs.append({f.name: np.load(f) for f in sorted((tmp_path / d).iterdir())})
+    rep = _json_line(r.stdout)
+    assert rep["steps"] == 2 and len(rep["step_ms"]) == 2 and rep["ms_per_step"] > 0 and rep["value"] > 0
+    assert rep["dtype"] == "fp64" and rep["higher_is_better"] is True and rep["status"] == 0
+    assert rep["check"] == "skipped" and rep["residual_inf"] is None
+    assert "profiled_solve" not in rep and "comm_bandwidth" not in rep
+    a, b = runs
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    _check_dump(a, n, n, 11)
+    assert np.array_equal(a["sample_rows.npy"], np.arange(n))
+
+
+def test_bench_dump_samples_a_large_inverse(native, tmp_path, monkeypatch):
+    """Above the size budget `--dump-outputs` keeps a seeded sample of rows and columns: the budget is
+    lowered here so that n = 203 is already "large" (20 of 203 rows, block 8: the last block row is
+    partial)."""
+    import argparse
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("gj_bench_script", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n, m, k = 203, 8, 20
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * n * k)
+    eng = native.Engine(native.host_device(1), native.self_comm(), n, m, "fp64")
+    eng.generate("random", 11)
+    assert eng.solve()["status"] == 0
+    args = argparse.Namespace(n=n, m=m, seed=11, dtype="fp64")
+    outs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(eng, args, 0, 1, False, str(tmp_path / d))
+        outs.append({f.name: np.load(f) for f in sorted((tmp_path / d).iterdir())})
+    for name in outs[0]:
+        assert np.array_equal(outs[0][name], outs[1][name]), name
+    _check_dump(outs[0], n, k, 11)
+    full = eng.download_local_rows()
+    rows, cols = outs[0]["sample_rows.npy"].astype(int), outs[0]["sample_cols.npy"].astype(int)
+    assert np.array_equal(outs[0]["inverse_rows.npy"], full[rows])
+    assert np.array_equal(outs[0]["inverse_cols.npy"], full[:, cols])
 
 
 def test_bench_self_launch_failure_exit_code():

@@ -28,7 +28,7 @@ def _verify(monkeypatch):
 def test_bench_under_torchrun_with_rccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", "29657", os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "1", "--warmup", "1", "--size", "4096", "--force-rccl"]
+           "--gpus", "1", "--full", "--steps", "1", "--warmup", "1", "--size", "4096", "--force-rccl"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -53,7 +53,7 @@ def test_cli_with_rccl_communicator():
 def _self_launch(*args, timeout=300):
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], cwd=ROOT, env=env,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", *args], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, out.stderr[-3000:]
     return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
