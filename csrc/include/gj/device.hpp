@@ -275,7 +275,9 @@ class Device {
   virtual void prepare_block_inverse(DType dt, const Layout& L, int variant) { (void)dt; (void)L; (void)variant; }
   // Partial pivoting (SolveOptions::pivot = Partial, `--pivot partial`).  Every local candidate
   // W_b (as in block_inverse) gets scores[b] = -max|W_b| and valid[b] = (max|W_b| >= thresh), so the
-  // common argmin (pivot_local) picks this rank's largest-magnitude candidate; its block alone is
+  // common argmin (pivot_local) picks this rank's largest-magnitude candidate (a used block: valid
+  // 0, score 0; a block with an Inf or a NaN entry is invalid -- the maximum keeps NaN, so one NaN
+  // entry cannot hide behind the finite ones); its block alone is
   // then copied out (gather_candidate: sel = K-major m x m, ld m; -I for an invalid record),
   // inverted by block_inverse on a one-block layout, and commit_candidate stores that inverse in
   // the candidate's slot of inv_t and clears rec->valid when the block is singular or, growth > 0,
@@ -328,6 +330,8 @@ class Device {
   // share of a root-agnostic exchange (an all-reduce sum carries the owner's values).
   virtual void zero_unless_owner(DType dt, void* buf, int64_t count, const int32_t* phys, int64_t p, int64_t k,
                                  int s) = 0;
+  // R[i*ldr + j] = Ht[j*m + i] for i, j < m: the pivot block's inverse (kept transposed, ld m)
+  // written row-major into a panel of leading dimension ldr.
   virtual void h_block(DType dt, void* R, int64_t ldr, const void* Ht, int64_t m, int s) = 0;
   virtual void gemm(DType dt, GemmOp op, ALayout al, int64_t M, int64_t N, int64_t K, const void* A,
                     int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int s,
@@ -355,6 +359,11 @@ class Device {
   static constexpr int kHashParts = 64;
   virtual void hash_rows(const void* base, int64_t ld_bytes, int64_t width_bytes, int64_t rows,
                          uint64_t* parts, int s) = 0;
+  // Non-finite values propagate through the three norms below: the maximum keeps NaN (a NaN row sum
+  // gives out[0] = NaN whatever the other rows hold, where fmax / std::max would drop it) and an Inf
+  // row sum gives +Inf, so that every gate that tests isfinite(residual) sees a broken inverse.
+  // Padding (global rows >= n, columns >= n, the pitch gap) is never read into a sum.
+  //
   // out[0] = max over local real rows of sum_{j<n} |X[r][j]|  (reference norm(), main.cpp:643-667).
   virtual void row_abs_max(DType dt, const void* X, int64_t ldx, const Layout& L, double* out,
                            int s) = 0;
@@ -364,6 +373,12 @@ class Device {
   // out[0] = max over local real rows r of sum_{j<n} |(A_loc * Full)[r][j] - delta(global(r), j)|
   // (matrix_mult_matrix + minus_i + norm, main.cpp:534-667, fused).  A_loc row-major ld npad,
   // Full = the whole inverse in natural row order (npad x npad).
+  // The product's inner sum runs over k < n on the host and over k < npad on the GPU: the two agree
+  // for the padded system the engine keeps, diag(A, I) and its inverse, i.e. whenever Full's rows
+  // >= n are 0 in the columns < n (or A's real rows are 0 in the columns >= n).  A's padding rows
+  // and Full's columns >= n never count.  NaN / Inf propagate as above, with one exception on the
+  // host, which skips the zero entries of A: a non-finite Full entry whose whole column of A_loc
+  // is 0 need not show there.
   virtual void residual(DType dt, const void* A, const void* Full, const Layout& L, double* out,
                         int s) = 0;
 };

@@ -34,6 +34,22 @@ __device__ inline void atomic_max_nonneg(double* addr, double v) {
   if (!(v >= 0.0)) v = __longlong_as_double(0x7ff8000000000000ll);  // NaN propagates as max
   atomicMax(reinterpret_cast<unsigned long long*>(addr), (unsigned long long)__double_as_longlong(v));
 }
+
+// The same order for reductions in registers: the bit pattern of a non-negative double, NaN (of
+// either sign) as the canonical quiet NaN, which lies above +Inf.  An integer maximum over these
+// keeps a NaN that fmax would drop.
+__device__ inline unsigned long long nonneg_key(double v) {
+  v = (v >= 0.0) ? fabs(v) : __longlong_as_double(0x7ff8000000000000ll);  // fabs: -0.0 -> +0.0
+  return (unsigned long long)__double_as_longlong(v);
+}
+__device__ inline unsigned long long wave_max_key(unsigned long long x) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const unsigned long long o = __shfl_xor(x, off, 64);
+    x = o > x ? o : x;
+  }
+  return x;
+}
 }  // namespace
 
 // ---------------------------------------------------------------- generate
@@ -343,19 +359,22 @@ __global__ __launch_bounds__(256) void candidate_maxabs_kernel(const T* __restri
     }
     return;
   }
-  double mx = 0.0;
+  // the maximum over the magnitudes' bit patterns (nonneg_key): a NaN entry wins, so it makes the
+  // candidate invalid below instead of hiding behind the finite entries as under fmax
+  unsigned long long key = 0;
   const int64_t total = (int64_t)m * m;
   for (int64_t e = threadIdx.x; e < total; e += blockDim.x) {
     const int64_t c = e / m, i = e - c * m;
-    mx = fmax(mx, fabs((double)Lt[c * ldl + (int64_t)b * m + i]));
+    const unsigned long long ke = nonneg_key(fabs((double)Lt[c * ldl + (int64_t)b * m + i]));
+    key = ke > key ? ke : key;
   }
-  __shared__ double red[4];
-  mx = wave_max_f64(mx);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __shared__ unsigned long long red[4];
+  key = wave_max_key(key);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = key;
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) mx = fmax(mx, red[w]);
-    mx = fmax(mx, red[0]);
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) key = red[w] > key ? red[w] : key;
+    const double mx = __longlong_as_double((long long)key);
     scores[b] = -mx;
     valid[b] = (mx >= thresh && isfinite(mx)) ? 1 : 0;
   }
@@ -705,9 +724,9 @@ __global__ __launch_bounds__(256) void residual_reduce_kernel(const double* part
     if (real)
       for (int q = 0; q < nparts; ++q) s += partial[r * nparts + q];
   }
-  double v = real ? s : 0.0;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+  // NaN-keeping maximum over the wave (fmax would return the finite operand: one finite lane -- a
+  // finite row, a padding row, a lane past `rows` -- and every NaN row sum of the wave was lost)
+  const double v = __longlong_as_double((long long)wave_max_key(nonneg_key(real ? s : 0.0)));
   if ((threadIdx.x & 63) == 0) atomic_max_nonneg(out, v);
 }
 

@@ -363,6 +363,101 @@ PYBIND11_MODULE(_C, mod) {
              d.residual(parse_dtype(dt), (const void*)A, (const void*)Full, lay(n, m, p, k),
                         (double*)out, S_MAIN);
              d.sync_stream(S_MAIN);
+           })
+      .def("row_abs_max_minus_i",
+           [lay](Device& d, const std::string& dt, U X, int64_t ldx, int64_t n, int64_t m, int64_t p,
+                 int64_t k, U out) {
+             d.row_abs_max_minus_i(parse_dtype(dt), (const void*)X, ldx, lay(n, m, p, k), (double*)out, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      // owner-side edits of a pivot step; the PieceMove fields default to "none"
+      .def("owner_edits",
+           [](Device& d, const std::string& dt, U At, int64_t ldl, U phys, int64_t p, int64_t k, int64_t j,
+              int64_t m, U lrow, U ht, U inv, U dst, int64_t ldd, U X, int64_t ldx, int64_t col0, int64_t w,
+              U eye, int64_t ld_eye) {
+             PieceMove mv;
+             mv.dst = (void*)dst;
+             mv.ldd = ldd;
+             mv.X = (void*)X;
+             mv.ldx = ldx;
+             mv.col0 = col0;
+             mv.w = w;
+             mv.eye = (void*)eye;
+             mv.ld_eye = ld_eye;
+             d.owner_edits(parse_dtype(dt), (void*)At, ldl, (const int32_t*)phys, p, k, j, m, (void*)lrow,
+                           (void*)ht, (const void*)inv, mv, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("dt"), py::arg("At"), py::arg("ldl"), py::arg("phys"), py::arg("p"), py::arg("k"), py::arg("j"),
+           py::arg("m"), py::arg("lrow"), py::arg("ht"), py::arg("inv"), py::arg("dst") = U(0), py::arg("ldd") = 0,
+           py::arg("X") = U(0), py::arg("ldx") = 0, py::arg("col0") = 0, py::arg("w") = 0, py::arg("eye") = U(0),
+           py::arg("ld_eye") = 0)
+      .def("take_rows",
+           [](Device& d, const std::string& dt, U dst, int64_t ldd, U X, int64_t ldx, U phys, int64_t p, int64_t k,
+              int64_t col0, int64_t w, int64_t m) {
+             d.take_rows(parse_dtype(dt), (void*)dst, ldd, (void*)X, ldx, (const int32_t*)phys, p, k, col0, w, m,
+                         S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      .def("sum_slices",
+           [](Device& d, const std::string& dt, U dst, U src, int64_t count, int64_t nslices) {
+             d.sum_slices(parse_dtype(dt), (void*)dst, (const void*)src, count, nslices, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      .def("zero_unless_owner",
+           [](Device& d, const std::string& dt, U buf, int64_t count, U phys, int64_t p, int64_t k) {
+             d.zero_unless_owner(parse_dtype(dt), (void*)buf, count, (const int32_t*)phys, p, k, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      .def("h_block",
+           [](Device& d, const std::string& dt, U R, int64_t ldr, U Ht, int64_t m) {
+             d.h_block(parse_dtype(dt), (void*)R, ldr, (const void*)Ht, m, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      // 64-bit partial sums into the kHashParts words at parts
+      .def("hash_rows",
+           [](Device& d, U base, int64_t ld_bytes, int64_t width_bytes, int64_t rows, U parts) {
+             d.hash_rows((const void*)base, ld_bytes, width_bytes, rows, (uint64_t*)parts, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      .def_property_readonly_static("kHashParts", [](py::object) { return (int)Device::kHashParts; })
+      .def("widen",
+           [](Device& d, const std::string& dt, U dst, int64_t ldd, U X, int64_t ldx, int64_t rows, int64_t cols) {
+             d.widen(parse_dtype(dt), (double*)dst, ldd, (const void*)X, ldx, rows, cols, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      .def("upload_convert",
+           [](Device& d, const std::string& dt, U X, int64_t ldx, U src, int64_t src_ld, int64_t rows,
+              int64_t cols) {
+             d.upload_convert(parse_dtype(dt), (void*)X, ldx, (const double*)src, src_ld, rows, cols, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      .def("add_diag",
+           [](Device& d, const std::string& dt, U A, int64_t ld, int64_t nd, double alpha) {
+             d.add_diag(parse_dtype(dt), (void*)A, ld, nd, alpha, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      // partial pivoting: candidate scores, the chosen block copied out, its inverse committed
+      .def("candidate_maxabs",
+           [lay](Device& d, const std::string& dt, U Lt, int64_t ldl, U scores, U valid, U used, int64_t n,
+                 int64_t m, int64_t p, int64_t k, double thresh) {
+             d.candidate_maxabs(parse_dtype(dt), (const void*)Lt, ldl, (double*)scores, (int32_t*)valid,
+                                (const int32_t*)used, lay(n, m, p, k), thresh, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      .def("gather_candidate",
+           [lay](Device& d, const std::string& dt, U sel, U Lt, int64_t ldl, U rec, int64_t n, int64_t m,
+                 int64_t p, int64_t k) {
+             d.gather_candidate(parse_dtype(dt), (void*)sel, (const void*)Lt, ldl, (const PivotRec*)rec,
+                                lay(n, m, p, k), S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      .def("commit_candidate",
+           [lay](Device& d, const std::string& dt, U inv_t, U inv1, U valid1, U score1, double growth, U rec,
+                 int64_t n, int64_t m, int64_t p, int64_t k) {
+             d.commit_candidate(parse_dtype(dt), (void*)inv_t, (const void*)inv1, (const int32_t*)valid1,
+                                (const double*)score1, growth, (PivotRec*)rec, lay(n, m, p, k), S_MAIN);
+             d.sync_stream(S_MAIN);
            });
   mod.def("hip_device", [](int idx) { return std::shared_ptr<Device>(new HipDevice(idx)); });
   mod.def("host_device", [](int nthreads) { return std::shared_ptr<Device>(new HostDevice(nthreads)); },
@@ -443,6 +538,40 @@ PYBIND11_MODULE(_C, mod) {
     for (auto& t : th) t.join();
     return msg;
   });
+  // len(values) virtual ranks on the host, each calling host_max with its own value on a
+  // LoopbackComm (async_: AsyncLoopbackComm) group: returns what every rank got back.
+  mod.def("loopback_host_max", [](std::vector<double> values, bool async_) {
+    const int p = (int)values.size();
+    if (p < 1) throw std::invalid_argument("loopback_host_max: no values");
+    auto hub = std::make_shared<LoopbackHub>(p);
+    std::vector<double> got(p, 0.0);
+    std::vector<std::string> err(p);
+    {
+      py::gil_scoped_release rel;
+      std::vector<std::thread> th;
+      for (int r = 0; r < p; ++r)
+        th.emplace_back([&, r] {
+          HostDevice dev(1);
+          try {
+            if (async_) {
+              AsyncLoopbackComm c(hub, r);
+              got[r] = c.host_max(dev, values[r]);
+            } else {
+              LoopbackComm c(hub, r);
+              got[r] = c.host_max(dev, values[r]);
+            }
+          } catch (const std::exception& e) {
+            err[r] = e.what();
+            hub->fail(err[r]);
+          }
+        });
+      for (auto& t : th) t.join();
+    }
+    for (const auto& e : err)
+      if (!e.empty()) throw std::runtime_error("loopback_host_max: " + e);
+    return got;
+  }, py::arg("values"), py::arg("async_") = false);
+  mod.attr("kHashParts") = (int)Device::kHashParts;
   mod.def("py_comm", [](py::object impl, int rank, int size) {
     return std::shared_ptr<Comm>(new PyComm(std::move(impl), rank, size));
   });

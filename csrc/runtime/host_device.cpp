@@ -283,7 +283,7 @@ void HostDevice::candidate_maxabs(DType dt, const void* Lt, int64_t ldl, double*
       for (int64_t i = 0; i < m; ++i) {
         const int64_t idx = c * ldl + b * m + i;
         const double v = dt == DType::F64 ? tp<double>(Lt)[idx] : (double)tp<float>(Lt)[idx];
-        mx = std::max(mx, std::fabs(v));
+        mx = max_keep_nan(mx, std::fabs(v));  // a NaN entry invalidates the candidate
       }
     scores[b] = -mx;
     valid[b] = (mx >= thresh && std::isfinite(mx)) ? 1 : 0;
@@ -470,7 +470,7 @@ void HostDevice::row_abs_max_minus_i(DType dt, const void* X, int64_t ldx, const
       const double v = dt == DType::F64 ? tp<double>(X)[r * ldx + j] : (double)tp<float>(X)[r * ldx + j];
       s += std::fabs(v - (j == gr ? 1.0 : 0.0));
     }
-    mx = std::max(mx, s);
+    mx = max_keep_nan(mx, s);
   }
   out[0] = mx;
 }
@@ -497,7 +497,7 @@ void HostDevice::row_abs_max(DType dt, const void* X, int64_t ldx, const Layout&
     double s = 0.0;
     for (int64_t j = 0; j < L.n; ++j)
       s += std::fabs(dt == DType::F64 ? tp<double>(X)[r * ldx + j] : (double)tp<float>(X)[r * ldx + j]);
-    mx = std::max(mx, s);
+    mx = max_keep_nan(mx, s);
   }
   out[0] = mx;
 }
@@ -522,7 +522,7 @@ void HostDevice::residual(DType dt, const void* A, const void* Full, const Layou
     rowres[r] = s;
   });
   double mx = 0.0;
-  for (double v : rowres) mx = std::max(mx, v);
+  for (double v : rowres) mx = max_keep_nan(mx, v);
   out[0] = mx;
 }
 

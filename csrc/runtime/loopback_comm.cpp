@@ -96,7 +96,7 @@ void LoopbackComm::allreduce_max(Device& dev, double* buf, size_t count, int s) 
   hub_->arrive_and_wait();
   for (int q = 0; q < size(); ++q) {
     const double* o = static_cast<const double*>(hub_->ptr[q]);
-    for (size_t i = 0; i < count; ++i) tmp[i] = (q == 0) ? o[i] : std::max(tmp[i], o[i]);
+    for (size_t i = 0; i < count; ++i) tmp[i] = (q == 0) ? o[i] : max_keep_nan(tmp[i], o[i]);
   }
   hub_->arrive_and_wait();
   dev.copy(buf, tmp.data(), count * sizeof(double), s);
@@ -137,7 +137,7 @@ double LoopbackComm::host_max(Device&, double v) {
   hub_->val[r_] = v;
   hub_->arrive_and_wait();
   double m = hub_->val[0];
-  for (int q = 1; q < size(); ++q) m = std::max(m, hub_->val[q]);
+  for (int q = 1; q < size(); ++q) m = max_keep_nan(m, hub_->val[q]);  // a NaN from any rank wins
   hub_->arrive_and_wait();
   return m;
 }

@@ -29,9 +29,11 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 
 #include <unistd.h>  // environ
 #include <thread>
@@ -710,6 +712,12 @@ double Engine::residual_file(const std::string& path, int nthreads, Status* stat
   return residual_rows(rows.data(), L_.n);
 }
 
+// A rank's share of a scalar agreement (the norms and the residual): NaN becomes +Inf before the
+// maximum over the ranks.  The devices' reductions keep NaN (Device::row_abs_max), but a MAX
+// all-reduce need not (RCCL, gloo: whichever operand their compare returns); +Inf is the maximum
+// under every NaN rule, and every gate tests isfinite().
+static double agreed_share(double v) { return std::isfinite(v) ? v : std::numeric_limits<double>::infinity(); }
+
 double Engine::result_norm_inf() {
   GJ_REQUIRE(solved_, "result_norm_inf: solve() first");
   double local = 0.0;
@@ -719,15 +727,15 @@ double Engine::result_norm_inf() {
     dev_.sync_stream(S_MAIN);
     local = dhost_[0];
   }
-  return comm_.host_max(dev_, local);
+  return comm_.host_max(dev_, agreed_share(local));
 }
 
 double Engine::norm_inf() {
-  if (local_norm_valid_) return comm_.host_max(dev_, local_norm_);  // from generate()
+  if (local_norm_valid_) return comm_.host_max(dev_, agreed_share(local_norm_));  // from generate()
   dev_.row_abs_max(opt_.dtype, X_, L_.npad, L_, dscratch_, S_MAIN);
   dev_.copy(dhost_, dscratch_, sizeof(double), S_MAIN);
   dev_.sync_stream(S_MAIN);
-  return comm_.host_max(dev_, dhost_[0]);
+  return comm_.host_max(dev_, agreed_share(dhost_[0]));
 }
 
 // ---------------------------------------------------------------- pivot search (SIDE stream)
@@ -1832,7 +1840,7 @@ double Engine::residual_common(const void* A, bool wide) {
   if (fullr != full) dev_.release(fullr);
   if (p > 1) dev_.release(full);
   last_residual_fp64_ = (rdt == DType::F64);
-  return comm_.host_max(dev_, local);
+  return comm_.host_max(dev_, agreed_share(local));
 }
 
 // p > 1 when the whole inverse does not fit on some rank: the reference's ring (matrix_mult_matrix,
@@ -1886,7 +1894,7 @@ double Engine::residual_streamed(const void* A, bool wide) {
   dev_.release(S);
   if (Sw) dev_.release(Sw);
   last_residual_fp64_ = (rdt == DType::F64);
-  return comm_.host_max(dev_, local);
+  return comm_.host_max(dev_, agreed_share(local));
 }
 
 double Engine::residual_generated(GenSpec g) {

@@ -134,6 +134,30 @@ def row_abs_max(X: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0) -> floa
     return float(out.item())
 
 
+def row_abs_max_minus_i(X: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0) -> float:
+    """max over this rank's real rows of sum_j |X[r][j] - delta(global row, j)|; NaN if a row holds one."""
+    out = torch.zeros(1, dtype=torch.float64, device=X.device)
+    device_for(X).row_abs_max_minus_i(_DT[X.dtype], _p(X), X.stride(0), n, m, p, k, _p(out))
+    return float(out.item())
+
+
+def h_block(Ht: torch.Tensor, ldr: int = 0) -> torch.Tensor:
+    """The m x m block kept transposed (ld m), written row-major: returns Ht^T (leading dimension ldr >= m)."""
+    m = Ht.shape[0]
+    assert Ht.shape == (m, m) and Ht.is_contiguous()
+    R = torch.zeros((m, max(ldr, m)), dtype=Ht.dtype, device=Ht.device)
+    device_for(Ht).h_block(_DT[Ht.dtype], _p(R), R.stride(0), _p(Ht), m)
+    return R[:, :m]
+
+
+def hash_rows(buf: torch.Tensor, ld_bytes: int, width_bytes: int, rows: int) -> int:
+    """The 64-bit verification hash (GJ_VERIFY) of `rows` rows of `width_bytes` bytes, pitch `ld_bytes`."""
+    dev = device_for(buf)
+    parts = torch.zeros(dev.kHashParts, dtype=torch.int64, device=buf.device)
+    dev.hash_rows(_p(buf), ld_bytes, width_bytes, rows, _p(parts))
+    return sum(int(v) & 0xFFFFFFFFFFFFFFFF for v in parts.cpu().tolist()) & 0xFFFFFFFFFFFFFFFF
+
+
 def residual(A_loc: torch.Tensor, Full: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0) -> float:
     out = torch.zeros(1, dtype=torch.float64, device=A_loc.device)
     device_for(A_loc).residual(_DT[A_loc.dtype], _p(A_loc), _p(Full), n, m, p, k, _p(out))
