@@ -52,7 +52,7 @@ class Error : public std::runtime_error {
 
 // Maximum that keeps NaN (std::max(a, b) drops a NaN b): the norms, the residual and the scalar
 // agreements between ranks, where a NaN must reach the isfinite() gates.
-inline double max_keep_nan(double a, double b) { return (a != a) ? a : (b != b || a < b) ? b : a; }
+GJ_HD inline double max_keep_nan(double a, double b) { return (a != a) ? a : (b != b || a < b) ? b : a; }
 
 [[noreturn]] void fail(const char* file, int line, const std::string& msg);
 

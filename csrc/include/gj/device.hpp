@@ -241,6 +241,10 @@ class Device {
   // compute inv(W) by Gauss-Jordan with partial pivoting (reference inverse_block, main.cpp:746-820),
   // write it transposed to inv_t[b*m*m + j*m + i] = inv(W)[i][j], its inf-norm to scores[b]
   // (block_norm, main.cpp:669-683), and valid[b] (0 when singular: |pivot| < thresh).
+  // A candidate that holds a NaN or an Inf entry, or whose sweep (in the block's own precision)
+  // produces one, is invalid: valid[b] = 0, scores[b] = 0, inv_t of that block unspecified.  An Inf
+  // or NaN pivot counts as singular, and the score's maximum keeps NaN, so that a NaN row sum cannot
+  // hide behind the finite rows; the other candidates of the launch are unaffected.
   // nlive = the number of local blocks with used == 0 (the caller knows every earlier pivot):
   // devices launch one workgroup per LIVE candidate only, so no used block is dispatched (its
   // workgroup would hold a whole CU's LDS / wave slots for nothing); scores / valid of used blocks

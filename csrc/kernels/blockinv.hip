@@ -167,7 +167,7 @@ __global__ __launch_bounds__(NTH) void block_inverse_kernel(const T* __restrict_
     }
     const int r = __builtin_amdgcn_readfirstlane(br < 0 ? kk : br);
     const T pivv = colv[par][r];
-    if (!(fabs((double)pivv) >= thresh)) {  // uniform across the workgroup
+    if (!pivot_usable((double)pivv, thresh)) {  // uniform across the workgroup
       singular = true;
       break;
     }
@@ -262,10 +262,9 @@ __global__ __launch_bounds__(NTH) void block_inverse_kernel(const T* __restrict_
     double rs = 0.0;
 #pragma unroll
     for (int q = 0; q < NTH / 64; ++q) rs += red[q][i];
-    mx = fmax(mx, rs);
+    mx = max_keep_nan(mx, rs);  // a NaN row sum must reach the validity test (fmax drops it)
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
+  mx = wave_max_keep_nan(mx);
   if (lane == 0) wmax[tid >> 6] = mx;
 
   // inverse, transposed: inv(W)[kinv[i]][prow[u]] = W_swept[i][u]  ->  inv_t[prow[u]*m + kinv[i]]
@@ -284,9 +283,8 @@ __global__ __launch_bounds__(NTH) void block_inverse_kernel(const T* __restrict_
   __syncthreads();
   if (tid == 0) {
     double sc = 0.0;
-    for (int q = 0; q < NTH / 64; ++q) sc = fmax(sc, wmax[q]);
-    scores[b] = sc;
-    valid[b] = isfinite(sc) ? 1 : 0;
+    for (int q = 0; q < NTH / 64; ++q) sc = max_keep_nan(sc, wmax[q]);
+    publish_score(scores, valid, b, sc);
   }
 }
 
@@ -349,7 +347,7 @@ __global__ __launch_bounds__(256) void block_inverse_generic(const T* __restrict
           bb = sv[q];
           ib = si[q];
         }
-      s_sing = !(bb >= thresh);
+      s_sing = !(bb >= 0.0 && pivot_usable(bb, thresh));  // bb = -1: nothing to choose (or only NaN)
       s_r = ib;
       if (!s_sing) {
         usedr[ib] = 1;
@@ -391,7 +389,7 @@ __global__ __launch_bounds__(256) void block_inverse_generic(const T* __restrict
   for (int i = tid; i < m; i += 256) {
     double s = 0.0;
     for (int j = 0; j < m; ++j) s += fabs((double)W[(int64_t)i * m + j]);
-    mx = fmax(mx, s);
+    mx = max_keep_nan(mx, s);  // (the scan above skips NaN entries: they end up in the row sums)
   }
   sv[tid] = mx;
   T* out = inv_t + (int64_t)b * m * m;
@@ -402,9 +400,8 @@ __global__ __launch_bounds__(256) void block_inverse_generic(const T* __restrict
   __syncthreads();
   if (tid == 0) {
     double sc = 0.0;
-    for (int q = 0; q < 256; ++q) sc = fmax(sc, sv[q]);
-    scores[b] = sc;
-    valid[b] = isfinite(sc) ? 1 : 0;
+    for (int q = 0; q < 256; ++q) sc = max_keep_nan(sc, sv[q]);
+    publish_score(scores, valid, b, sc);
   }
 }
 
@@ -600,7 +597,7 @@ __global__ __launch_bounds__(256) void block_inverse_blocked(const T* __restrict
 #pragma unroll
       for (int kk = 0; kk < PB; ++kk) rv[kk] = rowb[kk];
       const T piv = rv[jj];
-      if (!(fabs((double)piv) >= thresh)) {
+      if (!pivot_usable((double)piv, thresh)) {
         sing = true;  // every thread read the same pivot: a uniform exit
         break;
       }
@@ -702,14 +699,13 @@ __global__ __launch_bounds__(256) void block_inverse_blocked(const T* __restrict
   }
   double mx = 0.0;
 #pragma unroll
-  for (int s = 0; s < RPT; ++s) mx = fmax(mx, rs[s]);
-  mx = wave_max_f64(mx);
+  for (int s = 0; s < RPT; ++s) mx = max_keep_nan(mx, rs[s]);
+  mx = wave_max_keep_nan(mx);
   if (lane == 0) redn[wave] = mx;
   __syncthreads();
   if (tid == 0) {
-    const double sc = fmax(fmax(redn[0], redn[1]), fmax(redn[2], redn[3]));
-    scores[b] = sc;
-    valid[b] = isfinite(sc) ? 1 : 0;
+    const double sc = max_keep_nan(max_keep_nan(redn[0], redn[1]), max_keep_nan(redn[2], redn[3]));
+    publish_score(scores, valid, b, sc);
   }
 }
 

@@ -176,13 +176,10 @@ __global__ __launch_bounds__(64 * (NB + 1 + (LAY ? (NB - 1) / 3 : 0))) void bloc
         double sm = 0.0;
 #pragma unroll
         for (int w = 0; w < NB; ++w) sm += red[w][i];
-        mx = fmax(mx, sm);
+        mx = max_keep_nan(mx, sm);  // a NaN row sum must reach the validity test (fmax drops it)
       }
-      mx = wave_max_f64(mx);
-      if (lane == 0) {
-        scores[b] = mx;
-        valid[b] = isfinite(mx) ? 1 : 0;
-      }
+      mx = wave_max_keep_nan(mx);
+      if (lane == 0) publish_score(scores, valid, b, mx);
     } else if (lane == 0) {
       valid[b] = 0;
       scores[b] = 0.0;

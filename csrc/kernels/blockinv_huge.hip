@@ -140,7 +140,7 @@ __global__ __launch_bounds__(kFT) void huge_panel(T* __restrict__ Wc, int m, int
     if (tid < pb) rowb[tid] = Wc[(int64_t)(c0 + tid) * m + r];
     __syncthreads();  // B3: the pivot row's panel values
     const T piv = rowb[jj];
-    if (!(fabs((double)piv) >= thresh)) {
+    if (!pivot_usable((double)piv, thresh)) {
       if (tid == 0) in.flag[0] = 1;
       return;  // every thread read the same pivot: a uniform exit
     }
@@ -204,10 +204,11 @@ __global__ __launch_bounds__(256) void huge_rowsum(const T* __restrict__ Wc, int
   double s = 0.0;
   if (in.flag[0] == 0 && i < m)
     for (int u = 0; u < m; ++u) s += fabs((double)Wc[(int64_t)u * m + i]);
-  s = wave_max_f64(s);
+  s = wave_max_keep_nan(s);  // a NaN row sum must reach the validity test (fmax drops it)
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+  if (threadIdx.x == 0)
+    part[blockIdx.x] = max_keep_nan(max_keep_nan(red[0], red[1]), max_keep_nan(red[2], red[3]));
 }
 
 __global__ __launch_bounds__(256) void huge_probe(const int* ibase, int m, int32_t* probe) {
@@ -221,8 +222,8 @@ __global__ __launch_bounds__(256) void huge_score(const double* __restrict__ par
   const Ints in = ints_of(const_cast<int*>(ibase), m);
   __shared__ double red[4];
   double s = 0.0;
-  for (int q = threadIdx.x; q < nparts; q += 256) s = fmax(s, part[q]);
-  s = wave_max_f64(s);
+  for (int q = threadIdx.x; q < nparts; q += 256) s = max_keep_nan(s, part[q]);
+  s = wave_max_keep_nan(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -230,9 +231,8 @@ __global__ __launch_bounds__(256) void huge_score(const double* __restrict__ par
       valid[b] = 0;
       scores[b] = 0.0;
     } else {
-      const double sc = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-      scores[b] = sc;
-      valid[b] = isfinite(sc) ? 1 : 0;
+      const double sc = max_keep_nan(max_keep_nan(red[0], red[1]), max_keep_nan(red[2], red[3]));
+      publish_score(scores, valid, b, sc);
     }
   }
 }

@@ -413,13 +413,10 @@ __global__ __launch_bounds__(64 * (MP / 16 + 1 + (LAY ? (MP / 16 - 1) / 3 : 0)))
       double sm = 0.0;
 #pragma unroll
       for (int gq = 0; gq < 64 * NW / MP; ++gq) sm += redg[gq][i];
-      mx = fmax(mx, sm);
+      mx = max_keep_nan(mx, sm);  // a NaN row sum must reach the validity test (fmax drops it)
     }
-    mx = wave_max_f64(mx);
-    if (lane == 0) {
-      scores[b] = mx;
-      valid[b] = isfinite(mx) ? 1 : 0;
-    }
+    mx = wave_max_keep_nan(mx);
+    if (lane == 0) publish_score(scores, valid, b, mx);
     select_tail(sel, scores, valid, used, nblk, p, k);
   }
 }

@@ -267,7 +267,7 @@ struct PivotPanel {
     // pivot value, next column's entry, reciprocal; the pivot-row reads in its gaps
     T piv, nx, inv;
     chain_sel<0, J>(rs, rl, piv, nx, inv);  // rs is wave-uniform
-    singv |= ((c0 + J < m) && (none || !(fabs((double)piv) >= thresh))) ? 1u : 0u;
+    singv |= ((c0 + J < m) && (none || !pivot_usable((double)piv, thresh))) ? 1u : 0u;
     asm volatile("" : "+v"(singv));
     T u[RPL];
 #pragma unroll

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "gj/common.hpp"
+
 namespace gj {
 namespace kern {
 
@@ -41,6 +43,31 @@ __device__ __forceinline__ double wave_max_f64(double v) {
     v = fmax(join64(l[0], h[0]), join64(l[1], h[1]));
   }
   return v;
+}
+
+// Wave-wide maximum that keeps NaN (max_keep_nan; fmax drops a NaN operand), lane 0 holds the result
+// of all 64 lanes.  For a candidate's final score, outside the sweep loops.
+__device__ __forceinline__ double wave_max_keep_nan(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = max_keep_nan(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// The singularity test of a sweep step (workgroup-uniform: every thread holds the same pivot): the
+// pivot must reach thresh and be finite.  An Inf or NaN entry has the largest key of its column, so
+// it becomes the pivot; its reciprocal (0) would leave a finite block with a zero row.
+__device__ __forceinline__ bool pivot_usable(double piv, double thresh) {
+  const double a = fabs(piv);
+  return a >= thresh && a < __builtin_huge_val();
+}
+
+// A candidate's score and validity (Device::block_inverse): a non-finite score -- an entry of the
+// block or of its sweep was NaN or Inf -- makes the candidate invalid, with score 0.
+__device__ __forceinline__ void publish_score(double* __restrict__ scores, int32_t* __restrict__ valid, int b,
+                                              double sc) {
+  const bool ok = fabs(sc) < __builtin_huge_val();  // false for NaN
+  scores[b] = ok ? sc : 0.0;
+  valid[b] = ok ? 1 : 0;
 }
 
 // Wave-wide max of a uint32 (DPP inside rows, permlane swaps across rows), result in every lane.

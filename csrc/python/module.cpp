@@ -322,6 +322,49 @@ PYBIND11_MODULE(_C, mod) {
              d.release_pinned(h);
              return r;
            })
+      // block_inverse with the selection run by the launch's last workgroup (PivotSelectArgs; `used`
+      // doubles as used_w, as in Engine::select).  `done` is the caller's device counter (0 between
+      // launches).  p == 1: the whole selection, with a pinned host mirror read after the stream
+      // completes.  Returns (fused, mirror (step, found, phys, owner, logical, score) or None);
+      // fused == False: nothing was enqueued.
+      .def("block_inverse_select",
+           [lay](Device& d, const std::string& dt, U Lt, int64_t ldl, U inv_t, U scores, U valid, U used,
+                 int64_t n, int64_t m, int64_t p, int64_t k, double thresh, int64_t nlive, int t, U pos,
+                 U phys_at, U seq, U rec, U out, U done) {
+             PivotResult* h = nullptr;
+             if (p == 1) {
+               h = static_cast<PivotResult*>(d.alloc_pinned_coherent(sizeof(PivotResult)));
+               std::memset(h, 0, sizeof(PivotResult));
+               h->step = -1;
+             }
+             PivotSelectArgs sel;
+             sel.done = (int32_t*)done;
+             sel.t = (int32_t)t;
+             sel.pos = (const int32_t*)pos;
+             sel.pos_w = (int32_t*)pos;
+             sel.phys_at = (int32_t*)phys_at;
+             sel.used_w = (int32_t*)used;
+             sel.seq = (int32_t*)seq;
+             sel.rec = (PivotRec*)rec;
+             sel.out = (PivotResult*)out;
+             sel.host_out = h;
+             sel.single = p == 1 ? 1 : 0;
+             const bool fused =
+                 d.block_inverse_select(parse_dtype(dt), (const void*)Lt, ldl, (void*)inv_t, (double*)scores,
+                                        (int32_t*)valid, (const int32_t*)used, lay(n, m, p, k), thresh, nlive, sel,
+                                        S_MAIN);
+             d.sync_stream(S_MAIN);
+             py::object mirror = py::none();
+             if (h) {
+               mirror = py::make_tuple(h->step, h->found, h->phys, h->owner, h->logical, h->score);
+               d.release_pinned(h);
+             }
+             return py::make_tuple(fused, mirror);
+           },
+           py::arg("dt"), py::arg("Lt"), py::arg("ldl"), py::arg("inv_t"), py::arg("scores"), py::arg("valid"),
+           py::arg("used"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"), py::arg("thresh"),
+           py::arg("nlive"), py::arg("t"), py::arg("pos"), py::arg("phys_at"), py::arg("seq"), py::arg("rec"),
+           py::arg("out"), py::arg("done"))
       // Device-side latency of the batched block inverse: `reps` back-to-back launches on one
       // stream between two timing events (no host work in between); returns microseconds per call.
       .def("time_block_inverse",

@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <thread>
 #include <vector>
 
@@ -84,29 +85,46 @@ void gemm_t(GemmOp op, ALayout al, int64_t M, int64_t N, int64_t K, const T* A, 
 }
 
 // In-place Gauss-Jordan sweep on W (m x m, row-major) with partial pivoting over not-yet-used rows.
-// Returns false when singular (|pivot| < thresh).  prow[k] = pivot row of column k.
-template <typename T>
-bool sweep_inverse(std::vector<double>& W, int64_t m, double thresh, std::vector<int64_t>& prow) {
+// Returns false when singular (|pivot| < thresh, or an Inf / NaN pivot).  prow[k] = pivot row of column k.
+// The sweep runs in double whatever the block's type: `limit` is the largest finite value of that
+// type, and a value beyond it -- an overflow of the sweep in the block's own precision, which the
+// GPU kernels run in -- ends the sweep like a singular pivot (fp64: never taken, Inf > DBL_MAX aside).
+inline bool sweep_inverse(std::vector<double>& W, int64_t m, double thresh, std::vector<int64_t>& prow,
+                          double limit) {
   std::vector<char> used(m, 0);
   for (int64_t k = 0; k < m; ++k) {
     int64_t r = -1;
     double best = -1.0;
-    for (int64_t i = 0; i < m; ++i)
-      if (!used[i] && std::fabs(W[i * m + k]) > best) {
-        best = std::fabs(W[i * m + k]);
+    for (int64_t i = 0; i < m; ++i) {
+      if (used[i]) continue;
+      const double a = std::fabs(W[i * m + k]);
+      if (a != a) {  // a NaN is the column maximum, like the GPU's integer key: singular below
+        best = a;
+        r = i;
+        break;
+      }
+      if (a > best) {
+        best = a;
         r = i;
       }
-    if (!(best >= thresh)) return false;  // also catches NaN
+    }
+    if (!(best >= thresh && best < HUGE_VAL)) return false;  // NaN and Inf pivots included
     used[r] = 1;
     prow[k] = r;
     const double inv = 1.0 / W[r * m + k];
-    for (int64_t j = 0; j < m; ++j) W[r * m + j] *= inv;
+    for (int64_t j = 0; j < m; ++j) {
+      W[r * m + j] *= inv;
+      if (std::fabs(W[r * m + j]) > limit) return false;
+    }
     W[r * m + k] = inv;
     for (int64_t i = 0; i < m; ++i) {
       if (i == r) continue;
       const double f = W[i * m + k];
       if (f == 0.0) continue;
-      for (int64_t j = 0; j < m; ++j) W[i * m + j] -= f * W[r * m + j];
+      for (int64_t j = 0; j < m; ++j) {
+        W[i * m + j] -= f * W[r * m + j];
+        if (std::fabs(W[i * m + j]) > limit) return false;
+      }
       W[i * m + k] = -f * inv;
     }
   }
@@ -215,7 +233,10 @@ void HostDevice::add_diag(DType dt, void* A, int64_t ld, int64_t nd, double alph
 void HostDevice::block_inverse(DType dt, const void* Lt, int64_t ldl, void* inv_t, double* scores,
                                int32_t* valid, const int32_t* used, const Layout& L, double thresh, int64_t nlive,
                                int) {
+  (void)nlive;
   const int64_t m = L.m;
+  const double limit =
+      dt == DType::F64 ? std::numeric_limits<double>::max() : (double)std::numeric_limits<float>::max();
   parallel_for(L.nblk, nthreads_, [&](int64_t b) {
     const int64_t g = L.global_block(b);
     if (used[g]) {
@@ -229,19 +250,21 @@ void HostDevice::block_inverse(DType dt, const void* Lt, int64_t ldl, void* inv_
         W[i * m + j] = (dt == DType::F64) ? -tp<double>(Lt)[j * ldl + b * m + i]
                                           : -(double)tp<float>(Lt)[j * ldl + b * m + i];
     std::vector<int64_t> prow(m);
-    const bool ok = sweep_inverse<double>(W, m, thresh, prow);
-    if (!ok) {
+    const bool ok = sweep_inverse(W, m, thresh, prow, limit);
+    double sc = 0.0;
+    if (ok)
+      for (int64_t i = 0; i < m; ++i) {
+        double s = 0.0;
+        for (int64_t j = 0; j < m; ++j) s += std::fabs(W[i * m + j]);
+        sc = max_keep_nan(sc, s);  // a NaN row sum must reach the test below (std::max drops it)
+      }
+    // a non-finite score: an entry of the block or of its sweep was NaN or Inf (Device::block_inverse)
+    if (!ok || !std::isfinite(sc)) {
       valid[b] = 0;
       scores[b] = 0;
       return;
     }
-    double sc = 0.0;
-    for (int64_t i = 0; i < m; ++i) {
-      double s = 0.0;
-      for (int64_t j = 0; j < m; ++j) s += std::fabs(W[i * m + j]);
-      sc = std::max(sc, s);
-    }
-    valid[b] = std::isfinite(sc) ? 1 : 0;
+    valid[b] = 1;
     scores[b] = sc;
     // Y[k][prow[u]] = W[prow[k]][u]; inv_t[j*m + i] = Y[i][j]
     for (int64_t k = 0; k < m; ++k)

@@ -119,6 +119,22 @@ def block_inverse(Lt: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0, used
     return inv_t[:nblk], scores[:nblk], valid[:nblk]
 
 
+def block_inverse_select(Lt: torch.Tensor, inv_t: torch.Tensor, scores: torch.Tensor, valid: torch.Tensor,
+                         used: torch.Tensor, n: int, m: int, p: int, k: int, thresh: float, nlive: int, t: int,
+                         pos: torch.Tensor, phys_at: torch.Tensor, seq: torch.Tensor, rec: torch.Tensor,
+                         out: torch.Tensor, done: torch.Tensor):
+    """block_inverse with the pivot selection run by the launch's last workgroup (the engine's fused
+    step).  Every buffer is the caller's: ``done`` is the int32 counter that must be 0 between
+    launches, ``rec`` / ``out`` are 32-byte records.  p > 1: the local argmin -> ``rec``; p == 1: the
+    whole selection (``pos`` / ``phys_at`` / ``used`` / ``seq`` / ``out`` updated).  Returns
+    (fused, mirror): fused False means nothing was enqueued (the kernel family cannot fuse the
+    selection); mirror is the pinned host record (step, found, phys, owner, logical, score) at p == 1,
+    else None."""
+    return device_for(Lt).block_inverse_select(_DT[Lt.dtype], _p(Lt), Lt.stride(0), _p(inv_t), _p(scores),
+                                               _p(valid), _p(used), n, m, p, k, float(thresh), int(nlive), int(t),
+                                               _p(pos), _p(phys_at), _p(seq), _p(rec), _p(out), _p(done))
+
+
 def permute_blocks(X: torch.Tensor, m: int, dst_blk: torch.Tensor, colsrc: torch.Tensor) -> torch.Tensor:
     rows, ncols = X.shape
     nblk, Nr = rows // m, ncols // m

@@ -56,17 +56,29 @@ def _block_inverse(P: np.ndarray, thresh: float):
         piv = a[k, k]
         a[k, k + 1:] /= piv
         b[k] /= piv
-        for i in range(m):
-            if i != k:
-                f = a[i, k]
-                a[i, k + 1:] -= f * a[k, k + 1:]
-                b[i] -= f * b[k]
+        f = a[:, k].copy()  # every other row at once: the same products and differences, row by row
+        f[k] = 0.0
+        a[:, k + 1:] -= np.outer(f, a[k, k + 1:])
+        b -= np.outer(f, b[k])
     return b
 
 
-def gauss_jordan_reference(A: np.ndarray, m: int, p: int = 1, eps: float = 1e-15):
+def physical_pivots(pivots) -> list:
+    """The oracle's pivot sequence (logical positions under its physical row swaps) as the block rows
+    of the INPUT matrix, which is what the engine reports (stats["pivots"]: it never moves a row)."""
+    phys_at = list(range(len(pivots)))
+    out = []
+    for t, s in enumerate(pivots):
+        out.append(phys_at[s])
+        phys_at[t], phys_at[s] = phys_at[s], phys_at[t]
+    return out
+
+
+def gauss_jordan_reference(A: np.ndarray, m: int, p: int = 1, eps: float = 1e-15, return_gaps: bool = False):
     """Returns (inverse, pivots) where pivots[t] = logical block row chosen at step t, or raises
-    ArithmeticError('singular matrix')."""
+    ArithmeticError('singular matrix').  return_gaps: also the per-step relative gap between the best
+    and the second-best candidate score, (second - best) / best (inf with a single candidate): a
+    pivot sequence is only determined where no gap is within the rounding of the scores."""
     A = np.asarray(A, dtype=np.float64)
     n = A.shape[0]
     Nr = -(-n // m)
@@ -78,9 +90,10 @@ def gauss_jordan_reference(A: np.ndarray, m: int, p: int = 1, eps: float = 1e-15
     if abs(norm) < eps:
         raise ArithmeticError("singular matrix")
     thresh = eps * norm
-    pivots = []
+    pivots, gaps = [], []
     for t in range(Nr):
         best = None
+        cand = []
         for s in range(t, Nr):
             Y = _block_inverse(X[s * m:(s + 1) * m, t * m:(t + 1) * m], thresh)
             if Y is None:
@@ -88,6 +101,7 @@ def gauss_jordan_reference(A: np.ndarray, m: int, p: int = 1, eps: float = 1e-15
             sc = np.abs(Y).sum(axis=1).max()
             if not np.isfinite(sc):
                 continue
+            cand.append(sc)
             key = (sc, -(s % p), s // p)
             if best is None or key < best[0]:
                 best = (key, s, Y)
@@ -95,6 +109,8 @@ def gauss_jordan_reference(A: np.ndarray, m: int, p: int = 1, eps: float = 1e-15
             raise ArithmeticError("singular matrix")
         _, s, _ = best
         pivots.append(s)
+        cand.sort()
+        gaps.append((cand[1] - cand[0]) / cand[0] if len(cand) > 1 else np.inf)
         if s != t:
             rt, rs = slice(t * m, (t + 1) * m), slice(s * m, (s + 1) * m)
             X[rt], X[rs] = X[rs].copy(), X[rt].copy()
@@ -110,4 +126,6 @@ def gauss_jordan_reference(A: np.ndarray, m: int, p: int = 1, eps: float = 1e-15
             L = X[ri, rt].copy()
             X[ri] -= L @ X[rt]
             B[ri] -= L @ B[rt]
+    if return_gaps:
+        return B[:n, :n], pivots, gaps
     return B[:n, :n], pivots

@@ -586,6 +586,75 @@ def test_residual_nonfinite_propagates(ex, dtype, case):
         assert np.isnan(got), got
 
 
+# ------------------------------------------------------------------ block_inverse: non-finite candidates
+# (kernel family, m, dtypes): every family of the GPU over its own m range (the host executor has one
+# implementation and runs the same shapes)
+BI_FAMILIES = [("panel", 17, DTYPES), ("panel", 128, DTYPES), ("sweep", 64, DTYPES), ("co", 64, [torch.float64]),
+               ("panel", 200, [torch.float64]),  # the L2-image family
+               ("generic", 300, DTYPES), ("blocked", 300, DTYPES), ("huge", 300, DTYPES)]
+BI_CASES = [pytest.param(v, m, dt, id=f"{v}-{m}-{_DT[dt]}") for v, m, dts in BI_FAMILIES for dt in dts]
+BI_BAD = {1: "nan_5_7", 3: "inf_3_0", 5: "inf_last_col", 7: "overflow"}
+
+
+def _bi_blocks(m, dtype, base, with_bad):
+    """Nine candidates: well-conditioned blocks (dense: randn + 2 sqrt(m) I; diag: 5 I, where a NaN stays
+    in one row of the sweep instead of flooding the block) and, with_bad, four broken ones between
+    them (Device::block_inverse: a non-finite entry, or a sweep that produces one)."""
+    rng = np.random.default_rng(100 + m)
+    nblk = 9
+    if base == "dense":
+        W = rng.standard_normal((nblk, m, m)) + 2.0 * np.sqrt(m) * np.eye(m)
+    else:
+        W = np.broadcast_to(5.0 * np.eye(m), (nblk, m, m)).copy()
+    if with_bad:
+        big, small, tiny = (1e200, 1e-199, 1e-200) if dtype == torch.float64 else (1e20, 1e-19, 1e-20)
+        W[1][5, 7] = np.nan
+        W[3][3, 0] = np.inf
+        W[5][2, m - 1] = np.inf
+        # column 0 offers only rows 0 and 1: the pivot small, its reciprocal times `big` overflows
+        W[7][:2, :] = 0.0
+        W[7][:, :2] = 0.0
+        W[7][:2, :2] = [[small, big], [tiny, 1.0]]
+    return W.astype(_NP[dtype])
+
+
+def _bi_run(ex, dtype, W, thresh):
+    nblk, m = W.shape[0], W.shape[1]
+    Lt = _t(-W.reshape(nblk * m, m).T, ex)
+    inv_t = _t(np.full((nblk, m, m), SENT, _NP[dtype]), ex)
+    scores = _t(np.full(nblk, SENT, np.float64), ex)
+    valid = _t(np.full(nblk, -7, np.int32), ex)
+    used = _t(np.zeros(nblk, np.int32), ex)
+    _dev(ex).block_inverse(_DT[dtype], Lt.data_ptr(), nblk * m, inv_t.data_ptr(), scores.data_ptr(),
+                           valid.data_ptr(), used.data_ptr(), nblk * m, m, 1, 0, thresh, -1)
+    return _a(inv_t), _a(scores), _a(valid)
+
+
+@pytest.mark.parametrize("ex", EXEC)
+@pytest.mark.parametrize("base", ["dense", "diag"])
+@pytest.mark.parametrize("variant,m,dtype", BI_CASES)
+def test_block_inverse_nonfinite_candidate_is_invalid(ex, base, variant, m, dtype):
+    """A candidate that holds a NaN or an Inf, or whose sweep overflows, comes back valid = 0 and
+    score = 0 (it must never win the pivot selection with a score that a maximum took from the finite
+    rows only); its good neighbours are bit-identical to a launch without the broken blocks."""
+    thresh = 1e-300 if dtype == torch.float64 else 1e-30
+    C = gj.load_native()
+    C.set_block_inverse_variant(variant)
+    try:
+        inv_b, sc_b, va_b = _bi_run(ex, dtype, _bi_blocks(m, dtype, base, True), thresh)
+        inv_g, sc_g, va_g = _bi_run(ex, dtype, _bi_blocks(m, dtype, base, False), thresh)
+    finally:
+        C.set_block_inverse_variant("panel")
+    assert va_g.tolist() == [1] * 9
+    got = {name: (int(va_b[b]), float(sc_b[b])) for b, name in BI_BAD.items()}
+    assert got == {name: (0, 0.0) for name in BI_BAD.values()}, got
+    good = [b for b in range(9) if b not in BI_BAD]
+    assert va_b[good].tolist() == [1] * len(good)
+    assert np.array_equal(sc_b[good], sc_g[good])
+    assert np.array_equal(inv_b[good], inv_g[good])
+    assert np.isfinite(inv_b[good]).all() and np.isfinite(sc_b[good]).all()
+
+
 @pytest.mark.parametrize("ex", EXEC)
 def test_ops_wrappers(ex):
     from mpi_jordan_crazy_acceleration_amd import ops
