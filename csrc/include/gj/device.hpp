@@ -128,6 +128,11 @@ struct PieceMove {
   int64_t ld_eye = 0;
 };
 
+// Test probe: a short stable name of the kernel family (and build) that the calling thread's last
+// Device::gemm / gemm_batch ran ("host" on the host executor, the HIP names in kernels/gemm.hip).
+// Written at every launch site, read by nothing but tests: no effect on dispatch, no device work.
+inline thread_local const char* g_last_gemm_kernel = "";
+
 // One product of a batched small-GEMM launch (Device::gemm_batch): C (+)= A B, A K-major.
 struct GemmDesc {
   GemmOp op = GemmOp::Acc;
@@ -337,6 +342,14 @@ class Device {
   // R[i*ldr + j] = Ht[j*m + i] for i, j < m: the pivot block's inverse (kept transposed, ld m)
   // written row-major into a panel of leading dimension ldr.
   virtual void h_block(DType dt, void* R, int64_t ldr, const void* Ht, int64_t m, int s) = 0;
+  // C (+)= A B with the GemmExtra contract above.  Non-finite operands, the same on every executor:
+  // a NaN or an Inf of A or B inside the product's range (rows of the product, k < K, columns that
+  // are not skipped) reaches every element of C whose sum it is a term of, also where its factor is
+  // 0 (0 * NaN = 0 * Inf = NaN: no executor skips zero multipliers).  What a mask hides is not read
+  // at all: C in its zero columns / zero row blocks, C_in likewise, the skipped columns of C and B,
+  // rows k >= K and everything outside the M x N x K range, so a NaN there never shows.
+  // A leading dimension whose rows one tile of the chosen kernel cannot address with 32-bit byte
+  // offsets is refused with Status::BadArgs (GPU), never computed wrongly.
   virtual void gemm(DType dt, GemmOp op, ALayout al, int64_t M, int64_t N, int64_t K, const void* A,
                     int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int s,
                     const GemmExtra& ex = GemmExtra()) = 0;

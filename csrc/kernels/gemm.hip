@@ -75,6 +75,16 @@ using CfgSmall = Cfg<64, 32, 16, 2, 1, 8>;   // 128 threads: latency-bound panel
 using CfgSquarePf = Cfg<128, 128, 8, 2, 2, 2, 2>;  // fp32 deep trailing updates (110.5 TF/s)
 using CfgBigPf = Cfg<128, 128, 16, 2, 4, 2, 2>;    // fp64 deep updates the LDS-DMA kernel cannot take
 
+// last_gemm_kernel(): the family / build name of this thread's last launch (a test probe: one
+// thread-local pointer store per launch, nothing on the device, no effect on dispatch)
+template <typename CF> struct CfgName;
+template <> struct CfgName<CfgBig> { static constexpr const char* v = "big"; };
+template <> struct CfgName<CfgNarrow> { static constexpr const char* v = "narrow"; };
+template <> struct CfgName<CfgSmall> { static constexpr const char* v = "small"; };
+template <> struct CfgName<CfgSquarePf> { static constexpr const char* v = "squarepf"; };
+template <> struct CfgName<CfgBigPf> { static constexpr const char* v = "bigpf"; };
+const char* last_gemm_kernel() { return g_last_gemm_kernel; }
+
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 template <typename T>
@@ -465,17 +475,17 @@ struct GemmBatch {
 
 template <typename T, typename CF>
 __global__ __launch_bounds__(CF::NT, CF::WAVES_PER_SIMD) void gemm_batch_kernel(GemmBatch b) {
-  if (gemm_skipped(b.a[0])) return;  // one predicate per batch (fill: every product's, identical)
   const int bid = (int)blockIdx.x;
   int i = 0;
 #pragma unroll
   for (int k = 1; k < kMaxBatch; ++k) i += (k < b.n && bid >= b.start[k]) ? 1 : 0;
   // constant-index copies (a dynamically indexed kernel-argument array would go through scratch)
   switch (i) {
-    case 0: gemm_tile<T, 1, MODE_ACC, CF>(b.a[0], bid - b.start[0]); break;
-    case 1: gemm_tile<T, 1, MODE_ACC, CF>(b.a[1], bid - b.start[1]); break;
-    case 2: gemm_tile<T, 1, MODE_ACC, CF>(b.a[2], bid - b.start[2]); break;
-    default: gemm_tile<T, 1, MODE_ACC, CF>(b.a[3], bid - b.start[3]); break;
+    // (each product's own owner predicate, GemmDesc::ex: a uniform branch)
+    case 0: if (!gemm_skipped(b.a[0])) gemm_tile<T, 1, MODE_ACC, CF>(b.a[0], bid - b.start[0]); break;
+    case 1: if (!gemm_skipped(b.a[1])) gemm_tile<T, 1, MODE_ACC, CF>(b.a[1], bid - b.start[1]); break;
+    case 2: if (!gemm_skipped(b.a[2])) gemm_tile<T, 1, MODE_ACC, CF>(b.a[2], bid - b.start[2]); break;
+    default: if (!gemm_skipped(b.a[3])) gemm_tile<T, 1, MODE_ACC, CF>(b.a[3], bid - b.start[3]); break;
   }
 }
 
@@ -930,16 +940,15 @@ __global__ __launch_bounds__(256, 1) void gemm_lat_f64(GemmArgs g) {
 
 // gemm_batch_kernel with the register-fed tile (128 x 32 tiles: GemmArgs::tiles_* set for it)
 __global__ __launch_bounds__(256, 1) void gemm_lat_batch_f64(GemmBatch b) {
-  if (gemm_skipped(b.a[0])) return;
   const int bid = (int)blockIdx.x;
   int i = 0;
 #pragma unroll
   for (int k = 1; k < kMaxBatch; ++k) i += (k < b.n && bid >= b.start[k]) ? 1 : 0;
   switch (i) {  // constant-index copies, as in gemm_batch_kernel
-    case 0: lat_tile<MODE_ACC>(b.a[0], bid - b.start[0]); break;
-    case 1: lat_tile<MODE_ACC>(b.a[1], bid - b.start[1]); break;
-    case 2: lat_tile<MODE_ACC>(b.a[2], bid - b.start[2]); break;
-    default: lat_tile<MODE_ACC>(b.a[3], bid - b.start[3]); break;
+    case 0: if (!gemm_skipped(b.a[0])) lat_tile<MODE_ACC>(b.a[0], bid - b.start[0]); break;
+    case 1: if (!gemm_skipped(b.a[1])) lat_tile<MODE_ACC>(b.a[1], bid - b.start[1]); break;
+    case 2: if (!gemm_skipped(b.a[2])) lat_tile<MODE_ACC>(b.a[2], bid - b.start[2]); break;
+    default: if (!gemm_skipped(b.a[3])) lat_tile<MODE_ACC>(b.a[3], bid - b.start[3]); break;
   }
 }
 
@@ -964,6 +973,7 @@ static void launch_lat(const GemmArgs& a0, hipStream_t s) {
   a.tiles_n = (int)((a.N + 31) / 32);
   const int64_t nwg = (int64_t)a.tiles_m * a.tiles_n;
   if (nwg <= 0) return;
+  g_last_gemm_kernel = "lat64";
   hipLaunchKernelGGL((gemm_lat_f64<MODE>), dim3((unsigned)nwg), dim3(256), 0, s, a);
 }
 
@@ -1073,6 +1083,7 @@ static void launch_glds(const GemmArgs& a0, hipStream_t s) {
     if (nwg <= 0) return;
     a.group = glds_group();
     a.c_nt = glds_cnt(a.c_nt);
+    g_last_gemm_kernel = build0 == 33 ? "glds64:t128:b33:peel" : build0 == 32 ? "glds64:t128:b32:peel" : "glds64:t128:b23:peel";
     if (build0 == 33)
       hipLaunchKernelGGL((gemm_glds_f64<MODE, 3, 3, 8, 1, 128>), dim3((unsigned)nwg), dim3(glds::NT), 0, s, a);
     else if (build0 == 32)
@@ -1102,6 +1113,12 @@ static void launch_glds(const GemmArgs& a0, hipStream_t s) {
   // stages would exceed the LDS) stays.  Without the peel, 2.3 (3.3 was slower, above).
   const int forced = glds_build_forced();
   const int build = forced ? forced : a.build ? a.build : a.dense ? 25 : glds_peel() ? 33 : 23;
+  if (glds_peel())
+    g_last_gemm_kernel = build == 25 ? "glds64:t64:b25:peel" : build == 33 ? "glds64:t64:b33:peel"
+                         : build == 43 ? "glds64:t64:b43:peel" : build == 1623 ? "glds64:t64:b1623:peel"
+                                                                                : "glds64:t64:b23:peel";
+  else
+    g_last_gemm_kernel = build == 25 ? "glds64:t64:b25" : build == 33 ? "glds64:t64:b33" : "glds64:t64:b23";
   if (glds_peel()) {
     if (build == 25)
       hipLaunchKernelGGL((gemm_glds_f64<MODE, 2, 5, 8, 1>), dim3((unsigned)nwg), dim3(glds::NT), 0, s, a);
@@ -1375,6 +1392,7 @@ static void launch_glds32(const GemmArgs& a0, hipStream_t s) {
     if (nwg <= 0) return;
     a.group = 4;
     a.c_nt = glds_cnt(a.c_nt);
+    g_last_gemm_kernel = "glds32:t256";
     hipLaunchKernelGGL((gemm_glds_f32<MODE, 2, 3, 16, 1, 256>), dim3((unsigned)nwg), dim3(glds32::NT), 0, s, a);
     return;
   }
@@ -1397,6 +1415,7 @@ static void launch_glds32(const GemmArgs& a0, hipStream_t s) {
     const std::string v = e ? e : "";
     return v == "2.3" ? 23 : v == "3.3" ? 33 : 24;
   }();
+  g_last_gemm_kernel = "glds32:t128";
   if (glds_peel()) {
     if (b32 == 33)
       hipLaunchKernelGGL((gemm_glds_f32<MODE, 3, 3, 16, 1>), dim3((unsigned)nwg), dim3(glds32::NT), 0, s, a);
@@ -1415,8 +1434,29 @@ static bool glds32_ok(const GemmArgs& a) {
          a.lda * a.K * 4 < kRecords && a.ldb * a.K * 4 < kRecords && a.ldc * 128 * 4 < kRecords;
 }
 
+// gemm_tile addresses every operand from a per-tile (C, C_in, -C^T) or per-slice (A, B) base with
+// 32-bit byte offsets that must stay below the resource's extent: `rows` rows of `ld` elements and
+// `cols` more (the largest offset one tile forms, plus the element), or the buffer unit returns 0
+// for the load and drops the store.
+static bool tile_span_ok(int64_t ld, int64_t rows, int64_t cols, int64_t es) {
+  return ld >= 0 && ld <= (kRecords / es - cols) / (rows - 1);
+}
+template <typename T, int AL, int MODE, typename CF>
+static void check_cfg(const GemmArgs& a) {
+  constexpr int64_t ES = sizeof(T);
+  bool ok = tile_span_ok(a.ldb, CF::BK, CF::BN, ES) &&
+            (AL == 1 ? tile_span_ok(a.lda, CF::BK, CF::BM, ES) : tile_span_ok(a.lda, CF::BM, CF::BK, ES));
+  if (MODE != MODE_RESID) {
+    ok = ok && tile_span_ok(a.ldc, CF::BM, CF::BN, ES) && (!a.cin || tile_span_ok(a.ldcin, CF::BM, CF::BN, ES));
+    ok = ok && (!a.tneg || tile_span_ok(a.ldt, CF::BN, CF::BM, ES));
+  }
+  if (!ok) throw Error(Status::BadArgs, "gemm: leading dimension too large for 32-bit tile offsets");
+}
+
 template <typename T, int AL, int MODE, typename CF>
 static void launch_cfg(const GemmArgs& a0, hipStream_t s) {
+  check_cfg<T, AL, MODE, CF>(a0);
+  g_last_gemm_kernel = CfgName<CF>::v;
   GemmArgs a = a0;
   a.tiles_m = (int)((a.M + CF::BM - 1) / CF::BM);
   a.tiles_n = (int)((a.N + CF::BN - 1) / CF::BN);
@@ -1601,9 +1641,24 @@ void gemm_batch(DType dt, const GemmDesc* d, int n, hipStream_t s) {
   for (int e = 0; e < n && lat; ++e) {
     GemmArgs t{};
     t.lat_reg = d[e].ex.lat_reg;
+    // lat_tile: A / B offsets from the operand's origin (k < K), C / C_in / -C^T from the 128 x 32
+    // tile's; it has no row-block selection
+    const GemmExtra& x = d[e].ex;
     lat = lat_kernel(t) && d[e].lda * d[e].K * 8 < kRecords && d[e].ldb * d[e].K * 8 < kRecords &&
-          d[e].ldc * 128 * 8 < kRecords;
+          d[e].ldc * 128 * 8 < kRecords && (!x.c_in || x.ldc_in * 128 * 8 < kRecords) &&
+          (!x.tneg || x.ldtneg * 32 * 8 < kRecords) && x.rsel_m == 0;
   }
+  if (!lat) {  // the small register-staged tile: refuse what it cannot address, before any launch
+    for (int e = 0; e < n; ++e) {
+      if (d[e].M <= 0 || d[e].N <= 0) continue;
+      GemmArgs t{};
+      t.lda = d[e].lda; t.ldb = d[e].ldb; t.ldc = d[e].ldc;
+      t.cin = d[e].ex.c_in; t.ldcin = d[e].ex.ldc_in; t.tneg = d[e].ex.tneg; t.ldt = d[e].ex.ldtneg;
+      if (dt == DType::F64) check_cfg<double, 1, MODE_ACC, CF>(t);
+      else check_cfg<float, 1, MODE_ACC, CF>(t);
+    }
+  }
+  g_last_gemm_kernel = lat ? "batch:lat" : "batch:small";
   const int64_t TBM = lat ? 128 : CF::BM, TBN = lat ? 32 : CF::BN;
   GemmBatch b{};
   int tiles = 0;

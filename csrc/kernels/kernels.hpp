@@ -17,6 +17,10 @@ void gemm(DType dt, int op /*0 acc, 1 store*/, int a_kmajor, int64_t M, int64_t 
           hipStream_t s, const GemmExtra* ex = nullptr);
 // n independent small K-major GEMMs, one launch per 4 (small tiles; Store = C never read)
 void gemm_batch(DType dt, const GemmDesc* d, int n, hipStream_t s);
+// Test probe: the kernel family and build that this thread's last gemm / gemm_batch launched (or
+// "host" after HostDevice::gemm): small | narrow | big | bigpf | squarepf | lat64 |
+// glds64:t<64|128>:b<build>[:peel] | glds32:t<128|256> | batch:small | batch:lat.  "" before any.
+const char* last_gemm_kernel();
 int residual_nparts(int64_t N);
 int gemm_variant_id(const char* name);  // big | narrow | squarepf | bigpf | glds | auto; else throws
 void set_gemm_variant(int v);

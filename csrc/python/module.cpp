@@ -146,6 +146,17 @@ py::dict stats_to_dict(const SolveStats& st) {
   return d;
 }
 
+// GemmExtra's owner predicate from None or (address of the int32 pivot | None, p, k)
+void set_owner(GemmExtra& ex, const py::object& owner) {
+  if (owner.is_none()) return;
+  const py::tuple t = owner.cast<py::tuple>();
+  if (t.size() != 3) throw std::invalid_argument("owner: (phys, p, k)");
+  ex.owner_phys = t[0].is_none() ? nullptr : reinterpret_cast<const int32_t*>(t[0].cast<uintptr_t>());
+  ex.owner_p = t[1].cast<int64_t>();
+  ex.owner_k = t[2].cast<int64_t>();
+  if (ex.owner_p <= 0) throw std::invalid_argument("owner: p > 0");
+}
+
 py::array_t<double> to_array(const std::vector<double>& v, int64_t r, int64_t c) {
   py::array_t<double> a({r, c});
   if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), sizeof(double) * r * c);
@@ -197,6 +208,9 @@ PYBIND11_MODULE(_C, mod) {
   mod.def("set_lat_kernel", [](int mode) { kern::set_lat_kernel(mode); },
           "fp64 latency GEMMs on the register-fed small kernel: 1 / 0 for every launch, -1 per launch "
           "(GemmExtra::lat_reg; GJ_LAT_KERNEL)");
+  mod.def("last_gemm_kernel", [] { return std::string(kern::last_gemm_kernel()); },
+          "test probe: family / build name of the kernel this thread's last Device.gemm / gemm_batch ran "
+          "('host' on the host executor)");
   mod.def("set_lat_glds", [](bool on) { kern::set_lat_glds(on ? 1 : 0); },
           "every latency GEMM of >= 1024 rows on the LDS-DMA kernel (tests; the engine sets it per launch)");
 
@@ -213,8 +227,15 @@ PYBIND11_MODULE(_C, mod) {
               int64_t N, int64_t K, U A, int64_t lda, U B, int64_t ldb, U C, int64_t ldc, int64_t zc0,
               int64_t zc1, std::vector<int64_t> zero_rows, int64_t zh, U tneg, int64_t ldtneg, bool latency,
               int64_t tneg_cols, bool dense, U c_in, int64_t ldc_in, std::vector<int64_t> row_blocks,
-              int64_t row_block_m, int64_t skip_c0, int64_t skip_c1) {
+              int64_t row_block_m, int64_t skip_c0, int64_t skip_c1, py::object owner, bool lat_wide,
+              bool lat_reg, int glds_build, int glds_tile, int c_nt) {
              GemmExtra ex;
+             set_owner(ex, owner);
+             ex.lat_wide = lat_wide;
+             ex.lat_reg = lat_reg;
+             ex.glds_build = glds_build;
+             ex.glds_tile = glds_tile;
+             ex.c_nt = c_nt;
              ex.dense = dense;
              ex.skip_c0 = skip_c0;
              ex.skip_c1 = skip_c1;
@@ -249,20 +270,23 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("zh") = 0, py::arg("tneg") = U(0), py::arg("ldtneg") = 0, py::arg("latency") = false,
            py::arg("tneg_cols") = 0, py::arg("dense") = false, py::arg("c_in") = U(0), py::arg("ldc_in") = 0,
            py::arg("row_blocks") = std::vector<int64_t>(), py::arg("row_block_m") = 0, py::arg("skip_c0") = 0,
-           py::arg("skip_c1") = 0)
+           py::arg("skip_c1") = 0, py::arg("owner") = py::none(), py::arg("lat_wide") = false,
+           py::arg("lat_reg") = false, py::arg("glds_build") = 0, py::arg("glds_tile") = 0, py::arg("c_nt") = -1)
       .def("gemm_batch",
-           [](Device& d, const std::string& dt,
-              const std::vector<std::tuple<std::string, int64_t, int64_t, int64_t, U, int64_t, U, int64_t,
-                                           U, int64_t>>& ps) {
+           // product: (op, M, N, K, A, lda, B, ldb, C, ldc[, lat_reg[, owner]]), owner as in gemm
+           [](Device& d, const std::string& dt, const std::vector<py::tuple>& ps) {
              std::vector<GemmDesc> v(ps.size());
              for (size_t i = 0; i < ps.size(); ++i) {
-               const auto& t = ps[i];
+               const py::tuple& t = ps[i];
+               if (t.size() < 10 || t.size() > 12) throw std::invalid_argument("gemm_batch: 10 to 12 fields per product");
                GemmDesc& g = v[i];
-               g.op = std::get<0>(t) == "store" ? GemmOp::Store : GemmOp::Acc;
-               g.M = std::get<1>(t); g.N = std::get<2>(t); g.K = std::get<3>(t);
-               g.A = (const void*)std::get<4>(t); g.lda = std::get<5>(t);
-               g.B = (const void*)std::get<6>(t); g.ldb = std::get<7>(t);
-               g.C = (void*)std::get<8>(t); g.ldc = std::get<9>(t);
+               g.op = t[0].cast<std::string>() == "store" ? GemmOp::Store : GemmOp::Acc;
+               g.M = t[1].cast<int64_t>(); g.N = t[2].cast<int64_t>(); g.K = t[3].cast<int64_t>();
+               g.A = (const void*)t[4].cast<U>(); g.lda = t[5].cast<int64_t>();
+               g.B = (const void*)t[6].cast<U>(); g.ldb = t[7].cast<int64_t>();
+               g.C = (void*)t[8].cast<U>(); g.ldc = t[9].cast<int64_t>();
+               if (t.size() > 10) g.ex.lat_reg = t[10].cast<bool>();
+               if (t.size() > 11) set_owner(g.ex, t[11]);
              }
              d.gemm_batch(parse_dtype(dt), v.data(), (int)v.size(), S_MAIN);
              d.sync_stream(S_MAIN);

@@ -60,8 +60,8 @@ void gemm_t(GemmOp op, ALayout al, int64_t M, int64_t N, int64_t K, const T* A, 
     for (int z = 0; z < ex.nzr; ++z) zrow |= (i >= ex.zr[z] && i < ex.zr[z] + ex.zh);
     std::vector<double> acc(N, 0.0);
     for (int64_t k = 0; k < K; ++k) {
+      // (no shortcut for a == 0: 0 * NaN and 0 * Inf are NaN, as on the matrix cores -- Device::gemm)
       const double a = (al == ALayout::RowMajor) ? (double)A[i * lda + k] : (double)A[k * lda + i];
-      if (a == 0.0) continue;
       const T* b = B + k * ldb;
       for (int64_t j = 0; j < N; ++j)
         if (!(j >= ex.skip_c0 && j < ex.skip_c1)) acc[j] += a * (double)b[j];
@@ -460,6 +460,7 @@ void HostDevice::h_block(DType dt, void* R, int64_t ldr, const void* Ht, int64_t
 void HostDevice::gemm(DType dt, GemmOp op, ALayout al, int64_t M, int64_t N, int64_t K,
                       const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                       int, const GemmExtra& ex) {
+  g_last_gemm_kernel = "host";
   if (M <= 0 || N <= 0) return;
   if (dt == DType::F64)
     gemm_t<double>(op, al, M, N, K, tp<double>(A), lda, tp<double>(B), ldb, tp<double>(C), ldc,

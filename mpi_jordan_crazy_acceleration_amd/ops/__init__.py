@@ -39,7 +39,8 @@ def _p(t: torch.Tensor) -> int:
 def gemm(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, op: str = "acc", a_kmajor: bool = False,
          zero_cols=(0, 0), zero_rows=(), zero_row_height: int = 0, tneg: torch.Tensor = None,
          latency: bool = False, dense: bool = False, c_in: torch.Tensor = None, row_blocks=None,
-         row_block_m: int = 0, skip_cols=(0, 0)) -> torch.Tensor:
+         row_block_m: int = 0, skip_cols=(0, 0), owner=None, lat_wide: bool = False, lat_reg: bool = False,
+         glds_build: int = 0, glds_tile: int = 0, c_nt: int = -1) -> torch.Tensor:
     """C += A@B (op="acc") or C = A@B (op="store").  With a_kmajor, ``A`` is given as A^T (K x M).
 
     Elimination extras (op="acc"): C enters as 0 in the columns ``zero_cols`` = (c0, c1) and in the
@@ -52,7 +53,11 @@ def gemm(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, op: str = "acc", a_k
     ``row_block_m``: only those row blocks of C / A^T take part (GemmExtra::rsel); M = C's rows is
     then the physical height and the product runs over len(row_blocks) * row_block_m rows.
     ``skip_cols`` = (s0, s1): those output columns are neither read nor written (GemmExtra::skip_c0
-    / skip_c1; multiples of 128 on the GPU)."""
+    / skip_c1; multiples of 128 on the GPU).  ``owner`` = (phys, p, k): the owner-predicated launch --
+    nothing happens unless g = phys[0] (an int32 tensor on C's device; None: no predicate) is >= 0
+    and g % p == k.  ``lat_wide`` / ``lat_reg`` / ``glds_build`` / ``glds_tile`` / ``c_nt``: the
+    per-launch kernel choices of GemmExtra (which latency kernel, the fp64 LDS-DMA build and tile
+    width, non-temporal C loads | stores); the host executor ignores them."""
     assert A.dtype == B.dtype == C.dtype and A.stride(-1) == 1 and B.stride(-1) == 1 and C.stride(-1) == 1
     M, N = C.shape
     K = A.shape[0] if a_kmajor else A.shape[1]
@@ -69,22 +74,38 @@ def gemm(A: torch.Tensor, B: torch.Tensor, C: torch.Tensor, op: str = "acc", a_k
     device_for(C).gemm(_DT[C.dtype], op, a_kmajor, Msel, N, K, _p(A), A.stride(0), _p(B), B.stride(0), _p(C),
                        C.stride(0), int(zero_cols[0]), int(zero_cols[1]), [int(r) for r in zero_rows],
                        int(zero_row_height), tp, ldt, bool(latency), tcols, bool(dense), cp, ldci, rb,
-                       int(row_block_m), int(skip_cols[0]), int(skip_cols[1]))
+                       int(row_block_m), int(skip_cols[0]), int(skip_cols[1]), owner=_owner(owner, C),
+                       lat_wide=bool(lat_wide), lat_reg=bool(lat_reg), glds_build=int(glds_build),
+                       glds_tile=int(glds_tile), c_nt=int(c_nt))
     return C
+
+
+def _owner(owner, C):
+    if owner is None:
+        return None
+    phys, p, k = owner
+    if phys is not None:
+        assert phys.dtype == torch.int32 and phys.device == C.device and phys.numel() >= 1
+    return (None if phys is None else _p(phys), int(p), int(k))
 
 
 def gemm_batch(products) -> None:
     """Independent small products in one launch: each item is (op, At, B, C) with At = A^T (K x M),
-    op "acc" (C += A@B) or "store" (C = A@B).  All tensors share one dtype and device."""
+    op "acc" (C += A@B) or "store" (C = A@B), optionally followed by a dict of per-product extras:
+    ``lat_reg`` (bool) and ``owner`` = (phys, p, k) as in gemm().  All tensors share one dtype and
+    device."""
     if not products:
         return
     C0 = products[0][3]
     descs = []
-    for op, At, B, C in products:
+    for item in products:
+        op, At, B, C = item[:4]
+        extra = item[4] if len(item) > 4 else {}
         assert At.dtype == B.dtype == C.dtype == C0.dtype and At.stride(-1) == 1 and B.stride(-1) == 1
         assert C.stride(-1) == 1
         M, N = C.shape
-        descs.append((op, M, N, At.shape[0], _p(At), At.stride(0), _p(B), B.stride(0), _p(C), C.stride(0)))
+        descs.append((op, M, N, At.shape[0], _p(At), At.stride(0), _p(B), B.stride(0), _p(C), C.stride(0),
+                      bool(extra.get("lat_reg", False)), _owner(extra.get("owner"), C)))
     device_for(C0).gemm_batch(_DT[C0.dtype], descs)
 
 

@@ -331,8 +331,13 @@ def test_gemm_deep_auto_dispatch(native, M, N, K, dtype, variant):
     try:
         ops.gemm(A.t().contiguous().to(dtype).cuda(), B.to(dtype).cuda(), Cd, op="acc", a_kmajor=True,
                  zero_cols=(z0, z1), zero_rows=zr, zero_row_height=zh)
+        ran = native.last_gemm_kernel()
     finally:
         native.set_gemm_variant("auto")
+    if dtype == torch.float64:
+        assert ran == "glds64:t128:b23:peel"
+    else:
+        assert ran == ("glds32:t256" if M % 4 == 0 and N % 4 == 0 else "squarepf")
     assert (Cd.cpu().double() - ref).abs().max().item() < tol
 
 
