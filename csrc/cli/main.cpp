@@ -31,7 +31,12 @@
 //   --repeat R           time R solves, report the last (min also in --json)
 //   --out FILE           write the inverse (text, or .bin)
 //   --rhs ones|random|FILE  also solve A x = b (x = inv(A) b) and report ||A x - b||_inf
-//   --out-x FILE         write x (text, or .bin); implies --rhs ones unless --rhs is given
+//   --nrhs K             K right-hand sides, refined as a block (Engine::solve_rhs_block): ones ->
+//                        column j is (j+1) * ones, random -> column j seeded by seed + j, FILE holds
+//                        n * K values, row-major; --json gains per-column arrays, the printed residual
+//                        is the maximum over the columns
+//   --out-x FILE         write x (text, or .bin; n x K values, row-major); implies --rhs ones unless
+//                        --rhs is given
 //   --refine K           at most K refinement steps of x with the residual in fp64 (default: 10 for
 //                        fp32 solves, 2 for fp64; Engine::solve_rhs)
 //   --json               machine-readable report on stderr
@@ -92,6 +97,28 @@ static void json_report(const RunConfig& cfg, const RunReport& rep) {
       rhs += buf;
     }
     rhs += "]";
+    if (rep.nrhs > 1) {  // --nrhs K: one entry per column
+      auto arr = [&](const char* name, auto&& item) {
+        rhs += std::string(", \"") + name + "\": [";
+        for (size_t j = 0; j < rep.rhs_cols.size(); ++j) rhs += (j ? ", " : "") + item(rep.rhs_cols[j]);
+        rhs += "]";
+      };
+      auto num = [](double v) {
+        char b[64];
+        std::snprintf(b, sizeof b, "%.6e", v);
+        return std::string(b);
+      };
+      rhs += ", \"nrhs\": " + std::to_string(rep.nrhs);
+      arr("axb_residual_cols", [&](const RhsResult& c) { return num(c.residual); });
+      arr("axb_backward_error_cols", [&](const RhsResult& c) { return num(c.backward_error); });
+      arr("refine_steps_cols", [&](const RhsResult& c) { return std::to_string(c.steps); });
+      arr("refine_converged_cols", [&](const RhsResult& c) { return std::string(c.converged ? "true" : "false"); });
+      arr("axb_history_cols", [&](const RhsResult& c) {
+        std::string h = "[";
+        for (size_t i = 0; i < c.history.size(); ++i) h += (i ? ", " : "") + num(c.history[i]);
+        return h + "]";
+      });
+    }
   }
   std::fprintf(stderr,
                "{\"n\": %lld, \"m\": %lld, \"ranks\": %d, \"device\": \"%s\", \"comm\": \"%s\", "
@@ -171,6 +198,7 @@ int main(int argc, char* argv[]) {
       else if (a == "--repeat") cfg.repeats = std::atoi(val("--repeat"));
       else if (a == "--out") out_file = val("--out");
       else if (a == "--rhs") cfg.rhs = val("--rhs");
+      else if (a == "--nrhs") cfg.nrhs = std::atoi(val("--nrhs"));
       else if (a == "--out-x") x_file = val("--out-x");
       else if (a == "--refine") cfg.refine = std::atoi(val("--refine"));
       else if (a == "--json") json = true;
@@ -254,7 +282,7 @@ int main(int argc, char* argv[]) {
     std::printf("\nAx-b residual: %e\n", rep.rhs_residual);
   }
   if (!out_file.empty()) write_matrix_file(out_file, n, rep.inverse.data(), n);
-  if (!x_file.empty()) write_vector_file(x_file, n, rep.x.data());
+  if (!x_file.empty()) write_vector_file(x_file, n * rep.nrhs, rep.x.data());
   if (json) json_report(cfg, rep);
   int rc = 0;
   if (cfg.race_check) {

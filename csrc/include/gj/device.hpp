@@ -398,6 +398,37 @@ class Device {
   // is 0 need not show there.
   virtual void residual(DType dt, const void* A, const void* Full, const Layout& L, double* out,
                         int s) = 0;
+
+  // ---- a block of right-hand sides (Engine::solve_rhs_block) ----
+  // Y = C_in + sign * P V for 1 <= k <= kMaxRhs columns (else Status::BadArgs).
+  //   P     this rank's rows of a panel, L.rows x L.npad of dtype dt, leading dimension ldp
+  //   V     the whole block in natural row order, fp64, k columns, leading dimension ldv
+  //   C_in  fp64, L.rows x k, leading dimension ldc; null = 0; may alias Y
+  //   Y     fp64, L.rows x k, leading dimension ldy
+  //   sign  +1 or -1
+  //   active  int32[k] (device) or null: a column with active[j] == 0 is neither computed nor written
+  //   colmax  double[k] (device) or null: colmax[j] = max |Y[r][j]| over this rank's real rows
+  //           (global row < n), NaN kept as in row_abs_max; left untouched for an inactive column
+  // F64: fp64 throughout.  F32: V rounded to fp32 on load, the product accumulated in fp32, widened,
+  // then added to C_in in fp64.  The inner sum runs over the columns c < L.n.  Padding columns of P,
+  // the rows >= n of V and the pitch gap of every operand are never read (the norms' rule above);
+  // the padded local rows of Y are written as C_in (or 0).
+  static constexpr int kMaxRhs = 64;
+  virtual void panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                         int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign,
+                         const int32_t* active, double* colmax, int s) = 0;
+  // dst[g*ldd + j] = src[(q*max_nblk*m + b*m + e)*lds + j] for the global rows g = (b*p + q)*m + e < n
+  // and j < k: the rank-major rows Comm::allgather delivers (max_nblk*m rows per rank) into natural
+  // row order.  Rows >= n of dst are not written.
+  virtual void gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L,
+                                   int64_t k, int s) = 0;
+  // dst[r*ldd + j] = src[r*lds + j] for r < rows and the columns j < k with mask[j] != 0 (int32[k], device)
+  virtual void copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows,
+                                int64_t k, const int32_t* mask, int s) = 0;
 };
+
+// Test probe of Device::panel_rhs, like g_last_gemm_kernel: "host" on the host executor,
+// "rhs<16|32|64>:<f64|f32>:<vec|scalar>:s<split>" on the GPU.
+inline thread_local const char* g_last_rhs_kernel = "";
 
 }  // namespace gj

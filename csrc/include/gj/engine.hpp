@@ -124,6 +124,14 @@ struct RhsResult {
   bool converged = false;        // backward error <= tol
 };
 
+// Result of Engine::solve_rhs_block: one RhsResult per column, the residual sweeps of the longest
+// column group, and this rank's wall time of the call.
+struct RhsBlockResult {
+  std::vector<RhsResult> col;
+  int sweeps = 0;
+  double seconds = 0;
+};
+
 class Engine {
  public:
   Engine(Device& dev, Comm& comm, int64_t n, int64_t m, const SolveOptions& opt);
@@ -189,6 +197,22 @@ class Engine {
   // torch CUDA tensor: copied device-to-device, never through the host.
   RhsResult solve_rhs_device(const double* b, double* x, const void* dev_rows_f64, int64_t ld, int max_refine,
                              double tol);
+  // A X = B for a block of k right-hand sides, every column refined in fp64 by the rule of
+  // solve_rhs (its own RhsResult: converged at backward error <= tol, stopped after max_refine steps
+  // or when its residual did not halve, then the best iterate with that iterate's residual; a zero
+  // column gives x = 0).  Collective.  B and X are n x k, row-major (ldb, ldx >= k), full on every
+  // rank; A as in solve_rhs (gen / host_rows) or solve_rhs_device (dev_rows_f64).  The fp64 copy of
+  // A's rows is built once per call and the sweeps stay on the device (Device::panel_rhs streams
+  // each matrix once per sweep for all columns; per sweep the host sees the 2k column norms and
+  // sends back the column masks).  A column that has stopped is frozen: later sweeps neither
+  // compute nor write it.  More than Device::kMaxRhs columns run in groups.
+  RhsBlockResult solve_rhs_block(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
+                                 const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
+                                 int64_t ld, int max_refine, double tol);
+  // The same with B and X in device memory (fp64), e.g. torch CUDA tensors.
+  RhsBlockResult solve_rhs_block_device(const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx, int64_t k,
+                                        const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
+                                        int64_t ld, int max_refine, double tol);
   // Precision of the last residual: true = fp64 (always for fp64 solves; fp32 solves when it fits).
   bool residual_fp64() const { return last_residual_fp64_; }
   // ||A||_inf of the last solve's input (the reference's norm, taken at solve start) and
@@ -262,6 +286,9 @@ class Engine {
   SolveStats solve_steps();
   RhsResult solve_rhs_impl(const double* b, double* x, const GenSpec* gen, const double* host_rows,
                            const void* dev_rows, int64_t ld, int max_refine, double tol);
+  RhsBlockResult solve_rhs_block_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
+                                      bool on_device, const GenSpec* gen, const double* host_rows,
+                                      const void* dev_rows, int64_t ld, int max_refine, double tol);
   // GJ_VERIFY (SolveOptions::verify): hash slots of a panel, (d*C + 3d + 1) + 3 (2d + 2) of them:
   //   [chunk c][step j] Rb segment at MAIN's chunk update | pp[j] panel piece at its first consumer
   //   | la[j] look-ahead row segment at the look-ahead update | recs[j] gathered pivot records |

@@ -104,6 +104,13 @@ class HipDevice : public Device {
                    int s) override;
   void residual(DType dt, const void* A, const void* Full, const Layout& L, double* out,
                 int s) override;
+  void panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+                 const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign, const int32_t* active,
+                 double* colmax, int s) override;
+  void gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L, int64_t k,
+                           int s) override;
+  void copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows, int64_t k,
+                        const int32_t* mask, int s) override;
 
  private:
   void* scratch(size_t bytes, int slot);
@@ -114,8 +121,8 @@ class HipDevice : public Device {
   int bi_hint_ = -1;  // set_block_inverse_hint
   int tile_hint_ = 0;  // set_gemm_tile_hint
   std::vector<void*> events_;
-  void* scratch_[2] = {nullptr, nullptr};
-  size_t scratch_sz_[2] = {0, 0};
+  void* scratch_[3] = {nullptr, nullptr, nullptr};  // 2: panel_rhs K-slice partials
+  size_t scratch_sz_[3] = {0, 0, 0};
 };
 
 }  // namespace gj

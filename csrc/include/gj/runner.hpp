@@ -33,7 +33,11 @@ struct RunConfig {
   // A x = b after the inversion: "" (off), "ones", "random" (seeded by gen.seed), or a file of n
   // numbers (text / .bin).  x = inv(A) b, then ||A x - b||_inf.
   std::string rhs;
-  const double* rhs_input = nullptr;  // or a caller-owned n-vector
+  const double* rhs_input = nullptr;  // or a caller-owned n-vector (n x nrhs, row-major, when nrhs > 1)
+  // Right-hand sides (with rhs / rhs_input).  1: the one-vector path (Engine::solve_rhs).  > 1: the
+  // block path (Engine::solve_rhs_block); "ones": column j is (j + 1) * ones, "random": column j is
+  // seeded by gen.seed + j, a file holds n * nrhs values, row-major.
+  int nrhs = 1;
   bool keep_solution = false;         // return x in RunReport::x
   // iterative refinement of x with the residual in fp64 (Engine::solve_rhs): at most `refine`
   // steps (-1 = auto: 10 for fp32 solves, 2 for fp64), stop at backward error <= refine_tol
@@ -66,7 +70,12 @@ struct RunReport {
   bool residual_fp64 = true;        // precision of `residual` (fp32 solves: fp64 when it fits)
   double rhs_seconds = 0;           // x = inv(A) b (GEMV + all-gather), max over ranks
   std::vector<double> x_head;       // first min(n, print_max) entries of x
-  std::vector<double> x;            // n entries if keep_solution
+  std::vector<double> x;            // n entries if keep_solution (n x nrhs, row-major)
+  // nrhs > 1: one result per column; rhs_residual / rhs_backward_error / rhs_steps are then the
+  // maxima over the columns, rhs_converged holds when every column converged, rhs_history is the
+  // history of the column with the largest residual, x_head the head of column 0
+  int nrhs = 1;
+  std::vector<RhsResult> rhs_cols;
   // race_check: unordered conflicting accesses found (total, the first distinct ones described),
   // ops checked
   int64_t race_count = 0;

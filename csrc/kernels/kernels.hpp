@@ -126,5 +126,22 @@ void row_abs_max(DType dt, const void* X, int64_t ldx, const Layout& L, double* 
 // reduce residual partials: out = max over real local rows of sum_parts partial[r][*]
 void residual_reduce(const double* partial, int nparts, const Layout& L, double* out, hipStream_t s);
 
+
+// panel_rhs.hip: Device::panel_rhs / gather_rows_natural / copy_cols_masked.  scratch: the K-slice
+// partials, panel_rhs_scratch_bytes(L, k) bytes (for the split the launch will use).
+size_t panel_rhs_scratch_bytes(const Layout& L, int64_t k);
+void panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+               const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign, const int32_t* active,
+               double* colmax, void* scratch, hipStream_t s);
+void gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L, int64_t k,
+                         hipStream_t s);
+void copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows, int64_t k,
+                      const int32_t* mask, hipStream_t s);
+// Test hooks: K-split of the following panel_rhs launches (0 = auto, s >= 1 forces s; a launch never
+// runs an empty slice, so at most ceil(n / 16) take part), and the name of this thread's last
+// panel_rhs launch, "rhs<16|32|64>:<f64|f32>:<vec|scalar>:s<split>" ("host" on the host executor).
+void set_rhs_splitk(int s);
+const char* last_rhs_kernel();
+
 }  // namespace kern
 }  // namespace gj

@@ -165,6 +165,16 @@ py::array_t<double> to_array(const std::vector<double>& v, int64_t r, int64_t c)
 
 }  // namespace
 
+static py::dict rhs_info(const RhsResult& rr) {
+  py::dict info;
+  info["residual"] = rr.residual;
+  info["backward_error"] = rr.backward_error;
+  info["history"] = rr.history;
+  info["steps"] = rr.steps;
+  info["converged"] = rr.converged;
+  return info;
+}
+
 PYBIND11_MODULE(_C, mod) {
   mod.doc() = "MI355X-native block Gauss-Jordan inversion: native engine, HIP kernels, RCCL comm";
 
@@ -210,6 +220,11 @@ PYBIND11_MODULE(_C, mod) {
           "(GemmExtra::lat_reg; GJ_LAT_KERNEL)");
   mod.def("last_gemm_kernel", [] { return std::string(kern::last_gemm_kernel()); },
           "test probe: family / build name of the kernel this thread's last Device.gemm / gemm_batch ran "
+          "('host' on the host executor)");
+  mod.def("set_rhs_splitk", [](int s) { kern::set_rhs_splitk(s); },
+          "test hook: K-split of the following Device.panel_rhs launches on the GPU (0 = auto, s >= 1 forces s)");
+  mod.def("last_rhs_kernel", [] { return std::string(kern::last_rhs_kernel()); },
+          "test probe: 'rhs<16|32|64>:<f64|f32>:<vec|scalar>:s<split>' of this thread's last Device.panel_rhs "
           "('host' on the host executor)");
   mod.def("set_lat_glds", [](bool on) { kern::set_lat_glds(on ? 1 : 0); },
           "every latency GEMM of >= 1024 rows on the LDS-DMA kernel (tests; the engine sets it per launch)");
@@ -411,6 +426,44 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("dt"), py::arg("Lt"), py::arg("ldl"), py::arg("inv_t"), py::arg("scores"), py::arg("valid"),
            py::arg("used"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"), py::arg("thresh"),
            py::arg("reps"), py::arg("nlive") = -1)
+      // Device-side time of panel_rhs (Y = P V, every column active, column maxima on), and of the
+      // plain GEMM C = A B (row-major A, M x N x K) it is measured against: `reps` back-to-back
+      // launches between two timing events after one warm-up launch; microseconds per call.
+      .def("time_panel_rhs",
+           [lay](Device& d, const std::string& dt, U P, int64_t ldp, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U V, int64_t ldv, int64_t ncols, U Y, int64_t ldy, U colmax, int reps) {
+             py::gil_scoped_release rel;
+             const Layout L = lay(n, m, p, k);
+             const DType t = parse_dtype(dt);
+             auto run = [&] {
+               d.panel_rhs(t, (const void*)P, ldp, L, (const double*)V, ldv, ncols, nullptr, 0, (double*)Y, ldy, 1.0,
+                           nullptr, (double*)colmax, S_MAIN);
+             };
+             run();
+             const int e0 = d.create_event(true), e1 = d.create_event(true);
+             d.record(e0, S_MAIN);
+             for (int i = 0; i < reps; ++i) run();
+             d.record(e1, S_MAIN);
+             d.sync_stream(S_MAIN);
+             return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
+           })
+      .def("time_gemm_store",
+           [](Device& d, const std::string& dt, int64_t M, int64_t N, int64_t K, U A, int64_t lda, U B, int64_t ldb,
+              U C, int64_t ldc, int reps) {
+             py::gil_scoped_release rel;
+             const DType t = parse_dtype(dt);
+             auto run = [&] {
+               d.gemm(t, GemmOp::Store, ALayout::RowMajor, M, N, K, (const void*)A, lda, (const void*)B, ldb, (void*)C,
+                      ldc, S_MAIN);
+             };
+             run();
+             const int e0 = d.create_event(true), e1 = d.create_event(true);
+             d.record(e0, S_MAIN);
+             for (int i = 0; i < reps; ++i) run();
+             d.record(e1, S_MAIN);
+             d.sync_stream(S_MAIN);
+             return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
+           })
       .def("permute_blocks",
            [](Device& d, const std::string& dt, U dst, int64_t ldd, U X, int64_t ldx, int64_t nblk,
               int64_t m, int64_t Nr, U dst_blk, U colsrc) {
@@ -488,6 +541,30 @@ PYBIND11_MODULE(_C, mod) {
              d.sync_stream(S_MAIN);
            })
       .def_property_readonly_static("kHashParts", [](py::object) { return (int)Device::kHashParts; })
+      // Y = C_in + sign * P V for a block of right-hand sides; 0 = a null pointer
+      .def("panel_rhs",
+           [lay](Device& d, const std::string& dt, U P, int64_t ldp, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U V, int64_t ldv, int64_t ncols, U C_in, int64_t ldc, U Y, int64_t ldy, double sign, U active,
+                 U colmax) {
+             py::gil_scoped_release rel;
+             d.panel_rhs(parse_dtype(dt), (const void*)P, ldp, lay(n, m, p, k), (const double*)V, ldv, ncols,
+                         (const double*)C_in, ldc, (double*)Y, ldy, sign, (const int32_t*)active, (double*)colmax,
+                         S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("dt"), py::arg("P"), py::arg("ldp"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"),
+           py::arg("V"), py::arg("ldv"), py::arg("ncols"), py::arg("C_in"), py::arg("ldc"), py::arg("Y"),
+           py::arg("ldy"), py::arg("sign"), py::arg("active") = U(0), py::arg("colmax") = U(0))
+      .def("gather_rows_natural",
+           [lay](Device& d, U dst, int64_t ldd, U src, int64_t lds, int64_t n, int64_t m, int64_t p, int64_t ncols) {
+             d.gather_rows_natural((double*)dst, ldd, (const double*)src, lds, lay(n, m, p, 0), ncols, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      .def("copy_cols_masked",
+           [](Device& d, U dst, int64_t ldd, U src, int64_t lds, int64_t rows, int64_t ncols, U mask) {
+             d.copy_cols_masked((double*)dst, ldd, (const double*)src, lds, rows, ncols, (const int32_t*)mask, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
       .def("widen",
            [](Device& d, const std::string& dt, U dst, int64_t ldd, U X, int64_t ldx, int64_t rows, int64_t cols) {
              d.widen(parse_dtype(dt), (double*)dst, ldd, (const void*)X, ldx, rows, cols, S_MAIN);
@@ -770,6 +847,69 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("b"), py::arg("rows_f64"), py::arg("ld"), py::arg("max_refine") = -1, py::arg("tol") = 1e-15,
            "A x = b after solve(): x = inv(A) b by the native GEMV, refined in fp64 against this rank's rows "
            "of A given as an fp64 device array (Engine::solve_rhs_device); returns (x, info)")
+      .def("solve_rhs_block",
+           [](PyEngine& e, py::object B, py::object gen, py::object rows, uintptr_t rows_f64, int64_t ld,
+              uintptr_t b_dev, int64_t ldb, uintptr_t x_dev, int64_t ldx, int64_t ncols, int max_refine,
+              double tol) {
+             const int64_t n = e.eng->layout().n;
+             if (max_refine < 0) max_refine = e.eng->options().dtype == DType::F64 ? 2 : 10;
+             GenSpec g;
+             const GenSpec* gp = nullptr;
+             if (!gen.is_none()) {
+               const py::tuple t = gen.cast<py::tuple>();
+               g.kind = parse_gen(t[0].cast<std::string>());
+               g.seed = t[1].cast<uint64_t>();
+               gp = &g;
+             }
+             py::array_t<double, py::array::c_style | py::array::forcecast> hr;
+             const double* hrp = nullptr;
+             int64_t ldr = ld;
+             if (!rows.is_none()) {
+               hr = rows.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+               if (hr.ndim() != 2 || hr.shape(0) != e.eng->real_local_rows() || hr.shape(1) != n)
+                 throw std::invalid_argument("rows must be (real_rows, n) float64");
+               hrp = hr.data();
+               ldr = n;
+             } else if (rows_f64 && ld < n) {
+               throw std::invalid_argument("ld < n");
+             }
+             RhsBlockResult br;
+             py::object xo = py::none();
+             if (b_dev) {  // B and X in device memory (fp64, n x ncols)
+               if (!x_dev || ncols < 1 || ldb < ncols || ldx < ncols)
+                 throw std::invalid_argument("device B / X: ncols >= 1, ldb >= ncols, ldx >= ncols");
+               py::gil_scoped_release rel;
+               br = e.eng->solve_rhs_block_device(reinterpret_cast<const double*>(b_dev), ldb,
+                                                  reinterpret_cast<double*>(x_dev), ldx, ncols, gp, hrp,
+                                                  reinterpret_cast<const void*>(rows_f64), ldr, max_refine, tol);
+             } else {
+               auto b = B.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+               if (b.ndim() != 2 || b.shape(0) != n || b.shape(1) < 1)
+                 throw std::invalid_argument("B must be an (n, k) array, k >= 1");
+               const int64_t k = b.shape(1);
+               py::array_t<double> x({n, k});
+               {
+                 py::gil_scoped_release rel;
+                 br = e.eng->solve_rhs_block(b.data(), k, x.mutable_data(), k, k, gp, hrp,
+                                             reinterpret_cast<const void*>(rows_f64), ldr, max_refine, tol);
+               }
+               xo = x;
+             }
+             py::list infos;
+             for (const RhsResult& rc : br.col) infos.append(rhs_info(rc));
+             py::dict meta;
+             meta["sweeps"] = br.sweeps;
+             meta["seconds"] = br.seconds;
+             return py::make_tuple(xo, infos, meta);
+           },
+           py::arg("B") = py::none(), py::arg("gen") = py::none(), py::arg("rows") = py::none(),
+           py::arg("rows_f64") = 0, py::arg("ld") = 0, py::arg("b_dev") = 0, py::arg("ldb") = 0,
+           py::arg("x_dev") = 0, py::arg("ldx") = 0, py::arg("ncols") = 0, py::arg("max_refine") = -1,
+           py::arg("tol") = 1e-15,
+           "A X = B after solve() for a block of right-hand sides (Engine::solve_rhs_block): every column refined "
+           "in fp64 against A given as gen=(kind, seed), rows (this rank's fp64 rows, host) or rows_f64 / ld (an "
+           "fp64 device array).  B: an (n, k) host array -> returns (X, infos, meta); or b_dev / x_dev device "
+           "pointers (fp64, n x ncols) -> X is written in place and returned as None")
       .def("solve_rhs_generated",
            [](PyEngine& e, const std::string& kind, uint64_t seed,
               py::array_t<double, py::array::c_style | py::array::forcecast> b, int max_refine, double tol) {
@@ -908,6 +1048,8 @@ PYBIND11_MODULE(_C, mod) {
     if (d.contains("pivot_growth")) c.solve.pivot_growth = d["pivot_growth"].cast<double>();
     if (d.contains("profile")) c.solve.profile = d["profile"].cast<bool>();
     if (d.contains("rhs")) c.rhs = d["rhs"].cast<std::string>();
+    if (d.contains("nrhs")) c.nrhs = d["nrhs"].cast<int>();
+    if (c.nrhs < 1) throw std::invalid_argument("nrhs must be >= 1");
     if (d.contains("keep_solution")) c.keep_solution = d["keep_solution"].cast<bool>();
     if (d.contains("comm_timeout_s")) c.solve.comm_timeout_s = d["comm_timeout_s"].cast<double>();
     if (d.contains("residual")) {
@@ -931,7 +1073,7 @@ PYBIND11_MODULE(_C, mod) {
     py::array_t<double, py::array::c_style | py::array::forcecast> rhs_in;
     if (d.contains("rhs_input") && !d["rhs_input"].is_none()) {
       rhs_in = d["rhs_input"].cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
-      if (rhs_in.size() != c.n) throw std::invalid_argument("rhs_input must have n entries");
+      if (rhs_in.size() != c.n * c.nrhs) throw std::invalid_argument("rhs_input must have n * nrhs entries");
       c.rhs_input = rhs_in.data();
     }
     RunReport r;
@@ -968,7 +1110,12 @@ PYBIND11_MODULE(_C, mod) {
       o["refine_converged"] = r.rhs_converged;
       o["axb_backward_error"] = r.rhs_backward_error;
       o["x_head"] = r.x_head;
-      if (c.keep_solution) o["x"] = to_array(r.x, c.n, 1);
+      if (c.keep_solution) o["x"] = to_array(r.x, c.n, r.nrhs);
+      if (r.nrhs > 1) {
+        py::list cols;
+        for (const RhsResult& rc : r.rhs_cols) cols.append(rhs_info(rc));
+        o["axb_columns"] = cols;
+      }
     }
     return o;
   });

@@ -335,4 +335,21 @@ void AsyncHostDevice::residual(DType dt, const void* A, const void* Full, const 
   enqueue(s, [=] { inner_.residual(dt, A, Full, L, out, s); });
 }
 
+
+void AsyncHostDevice::panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                                int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign,
+                                const int32_t* active, double* colmax, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_rhs: 1 <= k <= 64 columns");
+  g_last_rhs_kernel = "host";
+  enqueue(s, [=] { inner_.panel_rhs(dt, P, ldp, L, V, ldv, k, C_in, ldc, Y, ldy, sign, active, colmax, s); });
+}
+void AsyncHostDevice::gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L,
+                                          int64_t k, int s) {
+  enqueue(s, [=] { inner_.gather_rows_natural(dst, ldd, src, lds, L, k, s); });
+}
+void AsyncHostDevice::copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows,
+                                       int64_t k, const int32_t* mask, int s) {
+  enqueue(s, [=] { inner_.copy_cols_masked(dst, ldd, src, lds, rows, k, mask, s); });
+}
+
 }  // namespace gj

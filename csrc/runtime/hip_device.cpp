@@ -402,4 +402,24 @@ void HipDevice::residual(DType dt, const void* A, const void* Full, const Layout
   check_launch();
 }
 
+
+void HipDevice::panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                          int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign,
+                          const int32_t* active, double* colmax, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_rhs: 1 <= k <= 64 columns");
+  void* part = scratch(kern::panel_rhs_scratch_bytes(L, k), 2);
+  kern::panel_rhs(dt, P, ldp, L, V, ldv, k, C_in, ldc, Y, ldy, sign, active, colmax, part, hs(streams_[s]));
+  check_launch();
+}
+void HipDevice::gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L,
+                                    int64_t k, int s) {
+  kern::gather_rows_natural(dst, ldd, src, lds, L, k, hs(streams_[s]));
+  check_launch();
+}
+void HipDevice::copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows, int64_t k,
+                                 const int32_t* mask, int s) {
+  kern::copy_cols_masked(dst, ldd, src, lds, rows, k, mask, hs(streams_[s]));
+  check_launch();
+}
+
 }  // namespace gj

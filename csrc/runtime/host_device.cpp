@@ -550,4 +550,58 @@ void HostDevice::residual(DType dt, const void* A, const void* Full, const Layou
   out[0] = mx;
 }
 
+
+void HostDevice::panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                           int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign,
+                           const int32_t* active, double* colmax, int) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_rhs: 1 <= k <= 64 columns");
+  g_last_rhs_kernel = "host";
+  std::vector<double> rowmax((size_t)std::max<int64_t>(L.rows, 1) * k, 0.0);
+  parallel_for(L.rows, nthreads_, [&](int64_t r) {
+    const bool real = L.global_row(r) < L.n;
+    for (int64_t j = 0; j < k; ++j) {
+      if (active && active[j] == 0) continue;
+      double y = C_in ? C_in[r * ldc + j] : 0.0;
+      if (real) {
+        double prod;
+        if (dt == DType::F64) {
+          double acc = 0.0;
+          for (int64_t c = 0; c < L.n; ++c) acc += tp<double>(P)[r * ldp + c] * V[c * ldv + j];
+          prod = acc;
+        } else {  // V rounded to fp32, fp32 accumulation, the product widened
+          float acc = 0.0f;
+          for (int64_t c = 0; c < L.n; ++c) acc += tp<float>(P)[r * ldp + c] * (float)V[c * ldv + j];
+          prod = (double)acc;
+        }
+        y += sign * prod;
+        rowmax[(size_t)(r * k + j)] = std::fabs(y);
+      }
+      Y[r * ldy + j] = y;
+    }
+  });
+  if (!colmax) return;
+  for (int64_t j = 0; j < k; ++j) {
+    if (active && active[j] == 0) continue;
+    double mx = 0.0;
+    for (int64_t r = 0; r < L.rows; ++r) mx = max_keep_nan(mx, rowmax[(size_t)(r * k + j)]);
+    colmax[j] = mx;
+  }
+}
+
+void HostDevice::gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L,
+                                     int64_t k, int) {
+  const int64_t per = L.max_nblk * L.m;
+  for (int64_t g = 0; g < L.n; ++g) {
+    const int64_t gb = g / L.m, e = g % L.m;
+    std::memcpy(dst + g * ldd, src + ((gb % L.p) * per + (gb / L.p) * L.m + e) * lds, sizeof(double) * (size_t)k);
+  }
+}
+
+void HostDevice::copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows, int64_t k,
+                                  const int32_t* mask, int) {
+  for (int64_t r = 0; r < rows; ++r)
+    for (int64_t j = 0; j < k; ++j)
+      if (mask[j] != 0) dst[r * ldd + j] = src[r * lds + j];
+}
+
 }  // namespace gj

@@ -740,4 +740,34 @@ void RaceCheckDevice::residual(DType dt, const void* A, const void* Full, const 
   inner_->residual(dt, A, Full, L, out, s);
 }
 
+
+void RaceCheckDevice::panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                                int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign,
+                                const int32_t* active, double* colmax, int s) {
+  std::vector<Acc> a;
+  if (k >= 1 && k <= kMaxRhs) {  // (the inner device refuses any other k before it touches memory)
+    a.push_back(R(rect(P, ldp, L.n, L.rows, (int64_t)dtype_size(dt)), "P"));
+    a.push_back(R(rect(V, ldv, k, L.n, 8), "V"));
+    if (C_in) a.push_back(R(rect(C_in, ldc, k, L.rows, 8), "C_in"));
+    if (active) a.push_back(R(span(active, 4 * k), "active"));
+    a.push_back(W(rect(Y, ldy, k, L.rows, 8), "Y"));
+    if (colmax) a.push_back(W(span(colmax, 8 * k), "colmax"));
+  }
+  check(s, "panel_rhs", a);
+  inner_->panel_rhs(dt, P, ldp, L, V, ldv, k, C_in, ldc, Y, ldy, sign, active, colmax, s);
+}
+void RaceCheckDevice::gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L,
+                                          int64_t k, int s) {
+  // rank q's real rows lie within its first nblk(q) * m rows; declared as the whole delivered rows
+  check(s, "gather_rows_natural", {R(rect(src, lds, k, L.p * L.max_nblk * L.m, 8), "gathered"),
+                                   W(rect(dst, ldd, k, L.n, 8), "natural")});
+  inner_->gather_rows_natural(dst, ldd, src, lds, L, k, s);
+}
+void RaceCheckDevice::copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows,
+                                       int64_t k, const int32_t* mask, int s) {
+  check(s, "copy_cols_masked", {R(rect(src, lds, k, rows, 8), "src"), R(span(mask, 4 * k), "mask"),
+                                W(rect(dst, ldd, k, rows, 8), "dst")});
+  inner_->copy_cols_masked(dst, ldd, src, lds, rows, k, mask, s);
+}
+
 }  // namespace gj

@@ -2136,6 +2136,210 @@ RhsResult Engine::solve_rhs_impl(const double* b, double* x, const GenSpec* gen,
   return rr;
 }
 
+// ---------------------------------------------------------------- A X = B, a block of columns
+RhsBlockResult Engine::solve_rhs_block(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
+                                       const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
+                                       int64_t ld, int max_refine, double tol) {
+  return solve_rhs_block_impl(B, ldb, X, ldx, k, false, gen, host_rows, dev_rows_f64, ld, max_refine, tol);
+}
+
+RhsBlockResult Engine::solve_rhs_block_device(const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx,
+                                              int64_t k, const GenSpec* gen, const double* host_rows,
+                                              const void* dev_rows_f64, int64_t ld, int max_refine, double tol) {
+  return solve_rhs_block_impl(B_dev, ldb, X_dev, ldx, k, true, gen, host_rows, dev_rows_f64, ld, max_refine, tol);
+}
+
+namespace {
+// device / pinned buffers of one call, released together (after the device went idle)
+struct BufSet {
+  Device& dev;
+  std::vector<void*> mem, pinned;
+  explicit BufSet(Device& d) : dev(d) {}
+  template <typename T>
+  T* get(size_t count, bool zero = true) {
+    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
+    void* p = dev.alloc(bytes);
+    mem.push_back(p);
+    if (zero) dev.memset0(p, bytes, S_MAIN);
+    return static_cast<T*>(p);
+  }
+  template <typename T>
+  T* get_pinned(size_t count) {
+    void* p = dev.alloc_pinned(sizeof(T) * std::max<size_t>(count, 1));
+    pinned.push_back(p);
+    return static_cast<T*>(p);
+  }
+  ~BufSet() {
+    try {
+      dev.sync_all();
+    } catch (...) {
+    }
+    for (void* p : mem) dev.release(p);
+    for (void* p : pinned) dev.release_pinned(p);
+  }
+};
+}  // namespace
+
+RhsBlockResult Engine::solve_rhs_block_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
+                                            bool on_device, const GenSpec* gen, const double* host_rows,
+                                            const void* dev_rows, int64_t ld, int max_refine, double tol) {
+  GJ_REQUIRE(solved_, "solve_rhs_block: solve() first");
+  GJ_REQUIRE(k >= 1 && ldb >= k && ldx >= k, "solve_rhs_block: k >= 1 columns, ldb >= k and ldx >= k");
+  GJ_REQUIRE(gen || host_rows || dev_rows || real_local_rows() == 0,
+             "solve_rhs_block: the matrix (generator or rows) is needed for the fp64 residual");
+  const auto t0 = std::chrono::steady_clock::now();
+  const int64_t m = L_.m, n = L_.n, p = L_.p;
+  const int64_t kw = std::min<int64_t>(k, Device::kMaxRhs);  // widest group = every buffer's leading dimension
+  const int64_t per = L_.max_nblk * m;                       // rows every rank sends to an all-gather
+  RhsBlockResult out;
+  out.col.resize((size_t)k);
+  BufSet bufs(dev_);
+  // A's local rows in fp64, once per call
+  double* Aw = bufs.get<double>((size_t)std::max<int64_t>(L_.rows, 1) * L_.npad, false);
+  if (gen) {
+    dev_.generate(DType::F64, Aw, L_, *gen, S_MAIN);
+  } else if (dev_rows) {  // zero + identity padding, then the real rows device-to-device
+    GenSpec z;
+    z.kind = GenKind::Zero;
+    dev_.generate(DType::F64, Aw, L_, z, S_MAIN);
+    const int64_t real = real_local_rows();
+    if (real > 0) dev_.copy2d(Aw, L_.npad * 8, dev_rows, ld * 8, n * 8, real, S_MAIN);
+  } else {
+    upload_rows_into(Aw, DType::F64, host_rows, ld);
+  }
+  dev_.row_abs_max(DType::F64, Aw, L_.npad, L_, dscratch_, S_MAIN);  // ||A||_inf (fp64)
+  dev_.copy(dhost_, dscratch_, sizeof(double), S_MAIN);
+  dev_.sync_stream(S_MAIN);
+  const double an = comm_.host_max(dev_, L_.nblk > 0 ? dhost_[0] : 0.0);
+
+  const size_t loc = (size_t)per * kw, nat = (size_t)std::max<int64_t>(n, 1) * kw;
+  double* Vb = bufs.get<double>(nat);     // B, natural row order
+  double* Vx = bufs.get<double>(nat);     // the iterate X, natural row order
+  double* Vr = bufs.get<double>(nat);     // the residual R, natural row order
+  double* Bloc = bufs.get<double>(loc);   // this rank's rows of B / X / R / the best iterate
+  double* Xloc = bufs.get<double>(loc);
+  double* Rloc = bufs.get<double>(loc);
+  double* best = bufs.get<double>(loc);
+  double* gath = bufs.get<double>(loc * (size_t)p);
+  double* dnorm = bufs.get<double>(2 * Device::kMaxRhs);   // ||r_j|| | ||x_j|| (this rank's rows)
+  int32_t* dflag = bufs.get<int32_t>(2 * Device::kMaxRhs);  // active | save-mask
+  double* hnorm = bufs.get_pinned<double>(2 * Device::kMaxRhs);
+  int32_t* hflag = bufs.get_pinned<int32_t>(2 * Device::kMaxRhs);
+  std::vector<double> hb;  // a device-resident B's columns on the host, for ||b_j|| only
+  std::vector<double> mine, all((size_t)(2 * Device::kMaxRhs) * p);
+
+  auto gather_natural = [&](double* dst, const double* src_loc) {
+    comm_.allgather(dev_, src_loc, gath, loc * sizeof(double), S_MAIN);
+    dev_.gather_rows_natural(dst, kw, gath, kw, L_, kw, S_MAIN);
+  };
+
+  for (int64_t c0 = 0; c0 < k; c0 += kw) {
+    const int64_t kg = std::min<int64_t>(kw, k - c0);
+    // B's columns of this group: natural order on the device, this rank's rows of it, ||b_j||
+    dev_.copy2d(Vb, kw * 8, B + c0, ldb * 8, kg * 8, n, S_MAIN);
+    for (int64_t b = 0; b < L_.nblk; ++b) {
+      const int64_t g0 = L_.global_block(b) * m;
+      if (g0 < n)
+        dev_.copy(Bloc + b * m * kw, Vb + g0 * kw, sizeof(double) * (size_t)(std::min<int64_t>(m, n - g0) * kw),
+                  S_MAIN);
+    }
+    std::vector<double> bn((size_t)kg, 0.0);
+    const double* bh = B + c0;
+    int64_t ldh = ldb;
+    if (on_device) {
+      hb.resize((size_t)n * kw);
+      dev_.copy(hb.data(), Vb, sizeof(double) * (size_t)n * kw, S_MAIN);
+      dev_.sync_stream(S_MAIN);
+      bh = hb.data();
+      ldh = kw;
+    }
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t j = 0; j < kg; ++j) bn[(size_t)j] = std::max(bn[(size_t)j], std::fabs(bh[i * ldh + j]));
+    for (double& v : bn)
+      if (v == 0) v = 1;
+
+    // x_0 = inv(A) b in the engine dtype, every column active
+    dev_.host_access(hflag, sizeof(int32_t) * 2 * Device::kMaxRhs, true);
+    for (int64_t j = 0; j < Device::kMaxRhs; ++j) hflag[j] = j < kg ? 1 : 0;
+    dev_.copy(dflag, hflag, sizeof(int32_t) * Device::kMaxRhs, S_MAIN);
+    dev_.panel_rhs(opt_.dtype, out_, L_.npad, L_, Vb, kw, kg, nullptr, 0, Xloc, kw, 1.0, nullptr,
+                   dnorm + Device::kMaxRhs, S_MAIN);
+    gather_natural(Vx, Xloc);
+
+    std::vector<int> active((size_t)kg, 1);
+    std::vector<double> best_rn((size_t)kg, 1e300), prev((size_t)kg, 1e300);
+    std::vector<RhsResult> bestr((size_t)kg);
+    RhsResult* rr = out.col.data() + c0;
+    for (int it = 0;; ++it) {
+      // r = b - A x on this rank's rows (fp64), then the whole residual on every rank
+      dev_.panel_rhs(DType::F64, Aw, L_.npad, L_, Vx, kw, kg, Bloc, kw, Rloc, kw, -1.0, dflag, dnorm, S_MAIN);
+      gather_natural(Vr, Rloc);
+      dev_.copy(hnorm, dnorm, sizeof(double) * 2 * Device::kMaxRhs, S_MAIN);
+      comm_.drain(dev_, S_MAIN);
+      dev_.host_access(hnorm, sizeof(double) * 2 * Device::kMaxRhs, false);
+      // the column norms over all ranks (a NaN from any rank wins)
+      mine.assign(hnorm, hnorm + 2 * Device::kMaxRhs);
+      comm_.host_allgather(dev_, mine.data(), all.data(), sizeof(double) * mine.size());
+      for (int64_t q = 0; q < p; ++q)
+        for (size_t e = 0; e < mine.size(); ++e)
+          mine[e] = q == 0 ? all[e] : max_keep_nan(mine[e], all[(size_t)q * mine.size() + e]);
+      out.sweeps = std::max(out.sweeps, it + 1);
+      // the per-column decision of solve_rhs
+      dev_.host_access(hflag, sizeof(int32_t) * 2 * Device::kMaxRhs, true);
+      bool any = false;
+      for (int64_t j = 0; j < kg; ++j) {
+        int32_t save = 0;
+        if (active[(size_t)j]) {
+          const double rn = mine[(size_t)j], xn = mine[(size_t)(Device::kMaxRhs + j)];
+          RhsResult& r = rr[j];
+          r.history.push_back(rn / bn[(size_t)j]);
+          r.residual = rn;
+          r.backward_error = rn / (an * xn + bn[(size_t)j]);
+          if (r.backward_error <= tol) {
+            r.converged = true;
+            active[(size_t)j] = 0;
+            save = 1;
+          } else {
+            if (rn < best_rn[(size_t)j]) {
+              best_rn[(size_t)j] = rn;
+              bestr[(size_t)j] = r;
+              save = 1;
+            }
+            if (it >= max_refine || (it > 0 && rn > 0.5 * prev[(size_t)j])) {  // budget spent / not contracting
+              if (rn > best_rn[(size_t)j]) {  // the best iterate (already saved), with its own residual
+                bestr[(size_t)j].history = r.history;
+                r = bestr[(size_t)j];
+              } else {
+                save = 1;
+              }
+              active[(size_t)j] = 0;
+            } else {
+              prev[(size_t)j] = rn;
+              r.steps = it + 1;
+            }
+          }
+        }
+        hflag[j] = active[(size_t)j];
+        hflag[Device::kMaxRhs + j] = save;
+        any = any || active[(size_t)j];
+      }
+      dev_.copy(dflag, hflag, sizeof(int32_t) * 2 * Device::kMaxRhs, S_MAIN);
+      dev_.copy_cols_masked(best, kw, Xloc, kw, L_.rows, kg, dflag + Device::kMaxRhs, S_MAIN);
+      if (!any) break;
+      // x += inv(A) r for the columns still active (engine dtype, added in fp64), then the whole X
+      dev_.panel_rhs(opt_.dtype, out_, L_.npad, L_, Vr, kw, kg, Xloc, kw, Xloc, kw, 1.0, dflag,
+                     dnorm + Device::kMaxRhs, S_MAIN);
+      gather_natural(Vx, Xloc);
+    }
+    // every column's returned iterate is in `best`
+    gather_natural(Vx, best);
+    dev_.copy2d(X + c0, ldx * 8, Vx, kw * 8, kg * 8, n, S_MAIN);
+    comm_.drain(dev_, S_MAIN);
+  }
+  out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return out;
+}
+
 void SelfComm::host_allgather(Device&, const void* send, void* recv, size_t bytes) {
   if (send != recv) std::memcpy(recv, send, bytes);
 }

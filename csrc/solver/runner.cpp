@@ -165,7 +165,41 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
       res = eng->residual_generated(cfg.gen);
     }
   }
-  if (!sh.b.empty()) {
+  if (!sh.b.empty() && cfg.nrhs > 1) {
+    const int64_t k = cfg.nrhs;
+    std::vector<double> x((size_t)cfg.n * k);
+    comm->barrier(*dev);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int refine = cfg.refine >= 0 ? cfg.refine : (cfg.solve.dtype == DType::F32 ? 10 : 2);
+    if (src && local.empty()) load();  // the fp64 rows of A (residual_rows keeps them in `local`)
+    const RhsBlockResult br = eng->solve_rhs_block(sh.b.data(), k, x.data(), k, k, src ? nullptr : &cfg.gen,
+                                                   src ? local.data() : nullptr, nullptr, cfg.n, refine,
+                                                   cfg.refine_tol);
+    const double tx = comm->host_max(
+        *dev, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    if (rank == 0) {
+      std::lock_guard<std::mutex> lk(sh.mu);
+      RunReport& r = sh.rep;
+      r.rhs_solved = true;
+      r.nrhs = (int)k;
+      r.rhs_cols = br.col;
+      r.rhs_converged = true;
+      size_t worst = 0;
+      for (size_t j = 0; j < br.col.size(); ++j) {
+        const RhsResult& c = br.col[j];
+        if (max_keep_nan(r.rhs_residual, c.residual) != r.rhs_residual) worst = j;
+        r.rhs_residual = max_keep_nan(r.rhs_residual, c.residual);
+        r.rhs_backward_error = max_keep_nan(r.rhs_backward_error, c.backward_error);
+        r.rhs_steps = std::max(r.rhs_steps, c.steps);
+        r.rhs_converged = r.rhs_converged && c.converged;
+      }
+      r.rhs_history = br.col[worst].history;
+      r.rhs_seconds = tx;
+      r.x_head.resize((size_t)nm);
+      for (int i = 0; i < nm; ++i) r.x_head[(size_t)i] = x[(size_t)i * k];
+      if (cfg.keep_solution) r.x = x;
+    }
+  } else if (!sh.b.empty()) {
     std::vector<double> x((size_t)cfg.n);
     comm->barrier(*dev);
     const auto t0 = std::chrono::steady_clock::now();
@@ -220,7 +254,33 @@ RunReport run_local(const RunConfig& cfg) {
     }
   }
   sh.input = cfg.input;
-  if (cfg.rhs_input) {
+  if (cfg.nrhs < 1) {
+    sh.rep.status = Status::BadArgs;
+    sh.rep.message = "bad arguments";
+    return sh.rep;
+  }
+  if (cfg.nrhs > 1 && (cfg.rhs_input || !cfg.rhs.empty())) {
+    const int64_t k = cfg.nrhs;
+    const size_t count = (size_t)cfg.n * k;
+    if (cfg.rhs_input) {
+      sh.b.assign(cfg.rhs_input, cfg.rhs_input + count);
+    } else if (cfg.rhs == "ones" || cfg.rhs == "random") {
+      const bool ones = cfg.rhs == "ones";
+      sh.b.resize(count);
+      for (int64_t i = 0; i < cfg.n; ++i)
+        for (int64_t j = 0; j < k; ++j)
+          sh.b[(size_t)(i * k + j)] =
+              ones ? (double)(j + 1)
+                   : gen_value((int)GenKind::Random, (cfg.gen.seed + (uint64_t)j) ^ 0x9E3779B97F4A7C15ull, cfg.n, i, 0);
+    } else {
+      const Status s = read_values_file(cfg.rhs, count, sh.b, cfg.host_threads);
+      if (s != Status::Ok) {
+        sh.rep.status = s;
+        sh.rep.message = (s == Status::CannotOpen ? "cannot open " : "cannot read ") + cfg.rhs;
+        return sh.rep;
+      }
+    }
+  } else if (cfg.rhs_input) {
     sh.b.assign(cfg.rhs_input, cfg.rhs_input + cfg.n);
   } else if (cfg.rhs == "ones") {
     sh.b.assign((size_t)cfg.n, 1.0);

@@ -67,9 +67,11 @@ class GaussJordan:
 
     def run(self, n: int, gen: str = "absdiff", seed: int = 0, file: Optional[str] = None,
             input: Optional[np.ndarray] = None, keep_inverse: bool = False, repeats: int = 1,
-            rhs=None, keep_solution: bool = False, profile: bool = False) -> dict:
-        """One CLI-equivalent run.  ``rhs``: None, "ones", "random", a file path, or an n-vector —
-        then x = inv(A) b is computed on the devices and ``axb_residual`` = ||A x - b||_inf reported."""
+            rhs=None, keep_solution: bool = False, profile: bool = False, nrhs: int = 1) -> dict:
+        """One CLI-equivalent run.  ``rhs``: None, "ones", "random", a file path, an n-vector or an
+        n x k matrix — then x = inv(A) b is computed on the devices, refined in fp64, and
+        ``axb_residual`` = ||A x - b||_inf reported.  ``nrhs`` > 1 (implied by a matrix): the block
+        path, all columns per sweep (``axb_columns``: one info per column, ``x``: n x nrhs)."""
         cfg = self._cfg(n)
         cfg.update(gen=gen, seed=int(seed), keep_inverse=keep_inverse, repeats=int(repeats),
                    keep_solution=bool(keep_solution), profile=bool(profile))
@@ -80,7 +82,11 @@ class GaussJordan:
         if isinstance(rhs, str):
             cfg["rhs"] = rhs
         elif rhs is not None:
-            cfg["rhs_input"] = np.ascontiguousarray(np.asarray(rhs, dtype=np.float64).reshape(-1))
+            r = np.asarray(rhs, dtype=np.float64)
+            if r.ndim == 2 and r.shape[1] > 1:
+                nrhs = r.shape[1]
+            cfg["rhs_input"] = np.ascontiguousarray(r.reshape(-1))
+        cfg["nrhs"] = int(nrhs)
         rep = load_native().run_local(cfg)
         rep["status_name"] = STATUS.get(rep["status"], "error")
         return rep
@@ -136,22 +142,28 @@ class GaussJordan:
         """A x = b for a CUDA tensor A through the engine (Engine::solve_rhs_device): x = inv(A) b by
         the native GEMV, then iterative refinement with the residual b - A x in fp64 against A's
         rows (an fp32 inverse refines to fp64 accuracy on a well-conditioned system, as the CLI's
-        --rhs path).  b: an n-vector or an n x k matrix (columns refined one by one).  Returns
-        (x on A's device in A's dtype, info per column)."""
+        --rhs path).  b: an n-vector, or an n x k matrix: then Engine::solve_rhs_block refines all
+        columns together on the device (one pass over each matrix per sweep, B and X never leave the
+        GPU).  Returns (x on A's device in A's dtype with b's shape, info per column)."""
         eng, _ = self._engine_resident(A)
         a64 = A.detach().to(torch.float64).contiguous()
+        if np.ndim(b) != 2 or np.shape(b)[1] == 1:  # one right-hand side: the one-vector path
+            torch.cuda.synchronize(a64.device)
+            bt = b.detach().to("cpu", torch.float64) if isinstance(b, torch.Tensor) else \
+                torch.as_tensor(np.asarray(b, dtype=np.float64))
+            x, info = eng.solve_rhs_device(np.ascontiguousarray(bt.reshape(-1).numpy()), a64.data_ptr(),
+                                           a64.stride(0), int(max_refine), float(tol))
+            return torch.from_numpy(x.reshape(bt.shape)).to(device=A.device, dtype=A.dtype), [info]
+        b64 = (b.detach() if isinstance(b, torch.Tensor) else torch.as_tensor(np.asarray(b, dtype=np.float64)))
+        b64 = b64.to(device=a64.device, dtype=torch.float64).contiguous()
+        if b64.shape[0] != a64.shape[0] or b64.shape[1] < 1:
+            raise ValueError("b must have n rows and at least one column")
+        x64 = torch.empty_like(b64)
         torch.cuda.synchronize(a64.device)
-        bt = b.detach().to("cpu", torch.float64) if isinstance(b, torch.Tensor) else \
-            torch.as_tensor(np.asarray(b, dtype=np.float64))
-        cols = bt.reshape(bt.shape[0], -1).numpy()
-        xs, infos = [], []
-        for j in range(cols.shape[1]):
-            x, info = eng.solve_rhs_device(np.ascontiguousarray(cols[:, j]), a64.data_ptr(), a64.stride(0),
-                                           int(max_refine), float(tol))
-            xs.append(x)
-            infos.append(info)
-        x = np.stack(xs, axis=1).reshape(bt.shape)
-        return torch.from_numpy(x).to(device=A.device, dtype=A.dtype), infos
+        _, infos, _ = eng.solve_rhs_block(rows_f64=a64.data_ptr(), ld=a64.stride(0), b_dev=b64.data_ptr(),
+                                          ldb=b64.stride(0), x_dev=x64.data_ptr(), ldx=x64.stride(0),
+                                          ncols=b64.shape[1], max_refine=int(max_refine), tol=float(tol))
+        return x64.to(A.dtype), list(infos)
 
 
 _HIP_DEVICES: dict = {}
@@ -171,18 +183,18 @@ def inverse(A, block_size: int = 128, **kw):
 def solve(A, b, block_size: int = 128, **kw):
     """Solve ``A x = b`` via the block Gauss-Jordan inverse.
 
-    A single right-hand side runs the native path (x = inv(A) b on the devices, the GEMV next to
-    the inverse's rows, refined in fp64); a matrix of right-hand sides multiplies by the returned
-    inverse on the host path.  A CUDA tensor A stays on its GPU: the engine solves it in place and
-    every right-hand side (vector or matrix columns) goes through Engine::solve_rhs_device, the
-    native GEMV plus fp64 refinement (never a bare ``inv @ b``)."""
+    Every right-hand side runs the native path, x = inv(A) b on the devices next to the inverse's
+    rows, refined in fp64 (never a bare ``inv @ b``): a vector through Engine::solve_rhs, a matrix
+    of k columns through Engine::solve_rhs_block, which refines all columns per sweep with one pass
+    over each matrix and gives every column the accuracy of the one-vector call.  A CUDA tensor A
+    stays on its GPU (Engine::solve_rhs_device / solve_rhs_block_device); X keeps b's shape."""
     is_torch = isinstance(A, torch.Tensor)
     if is_torch and A.is_cuda:
         gj = GaussJordan(block_size=block_size, residual="never", **kw)
         x, _ = gj.solve_resident(A, b)
         return x
     bn = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, dtype=np.float64)
-    if bn.ndim == 1:
+    if bn.ndim in (1, 2):
         a = A.detach().to("cpu", torch.float64).numpy() if is_torch else np.asarray(A, dtype=np.float64)
         gj = GaussJordan(block_size=block_size, residual="never", **kw)
         rep = gj.run(a.shape[0], input=a, rhs=bn, keep_solution=True)
@@ -190,12 +202,9 @@ def solve(A, b, block_size: int = 128, **kw):
             raise SingularMatrixError("singular matrix")
         if rep["status"] != 0:
             raise RuntimeError(rep["message"] or rep["status_name"])
-        x = rep["x"].reshape(-1)
+        x = rep["x"].reshape(bn.shape)
         return torch.from_numpy(x).to(device=A.device, dtype=A.dtype) if is_torch else x
-    inv = inverse(A, block_size=block_size, **kw)
-    if isinstance(inv, torch.Tensor):
-        return inv @ (b if isinstance(b, torch.Tensor) else torch.as_tensor(b, dtype=inv.dtype))
-    return inv @ np.asarray(b, dtype=np.float64)
+    raise ValueError("b must be an n-vector or an n x k matrix")
 
 
 def run(n: int, m: int, ranks: int = 1, device: str = "auto", gen: str = "absdiff", seed: int = 0,

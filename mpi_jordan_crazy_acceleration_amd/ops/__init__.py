@@ -199,3 +199,46 @@ def residual(A_loc: torch.Tensor, Full: torch.Tensor, n: int, m: int, p: int = 1
     out = torch.zeros(1, dtype=torch.float64, device=A_loc.device)
     device_for(A_loc).residual(_DT[A_loc.dtype], _p(A_loc), _p(Full), n, m, p, k, _p(out))
     return float(out.item())
+
+
+def panel_rhs(P: torch.Tensor, V: torch.Tensor, Y: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0,
+              C_in: torch.Tensor = None, sign: float = 1.0, active: torch.Tensor = None,
+              colmax: torch.Tensor = None, ncols: int = None) -> torch.Tensor:
+    """Y = C_in + sign * P @ V over the columns c < n (Device::panel_rhs): ``P`` this rank's rows of a
+    panel (fp64 / fp32, rows x >= n), ``V`` the whole block in natural row order (fp64, >= n rows),
+    ``C_in`` fp64 or None (0; may be Y itself), ``active`` int32[ncols] or None (columns with 0 are
+    neither computed nor written), ``colmax`` float64[ncols] or None (max |Y| over the real rows of
+    each active column, NaN kept).  All are views with unit column stride; ``ncols`` defaults to
+    Y's width (1..64, else ValueError)."""
+    assert V.dtype == Y.dtype == torch.float64 and P.stride(-1) == 1 and V.stride(-1) == 1 and Y.stride(-1) == 1
+    ncols = Y.shape[1] if ncols is None else int(ncols)
+    cp, ldc = 0, 0
+    if C_in is not None:
+        assert C_in.dtype == torch.float64 and C_in.stride(-1) == 1
+        cp, ldc = _p(C_in), C_in.stride(0)
+    if active is not None:
+        assert active.dtype == torch.int32 and active.is_contiguous()
+    if colmax is not None:
+        assert colmax.dtype == torch.float64 and colmax.is_contiguous()
+    device_for(Y).panel_rhs(_DT[P.dtype], _p(P), P.stride(0), n, m, p, k, _p(V), V.stride(0), ncols, cp, ldc, _p(Y),
+                            Y.stride(0), float(sign), 0 if active is None else _p(active),
+                            0 if colmax is None else _p(colmax))
+    return Y
+
+
+def gather_rows_natural(dst: torch.Tensor, src: torch.Tensor, n: int, m: int, p: int, ncols: int = None) -> torch.Tensor:
+    """dst[g] = the row of global index g < n out of ``src``, the rank-major rows an all-gather
+    delivers (ceil(Nr / p) * m rows per rank); rows >= n of dst are not written (fp64 views)."""
+    assert dst.dtype == src.dtype == torch.float64 and dst.stride(-1) == 1 and src.stride(-1) == 1
+    ncols = dst.shape[1] if ncols is None else int(ncols)
+    device_for(dst).gather_rows_natural(_p(dst), dst.stride(0), _p(src), src.stride(0), n, m, p, ncols)
+    return dst
+
+
+def copy_cols_masked(dst: torch.Tensor, src: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """dst[:, j] = src[:, j] for the columns with mask[j] != 0 (fp64 views, int32 mask)."""
+    assert dst.dtype == src.dtype == torch.float64 and dst.stride(-1) == 1 and src.stride(-1) == 1
+    assert mask.dtype == torch.int32 and mask.is_contiguous() and dst.shape == src.shape
+    device_for(dst).copy_cols_masked(_p(dst), dst.stride(0), _p(src), src.stride(0), dst.shape[0], dst.shape[1],
+                                     _p(mask))
+    return dst

@@ -205,6 +205,29 @@ class DistributedGaussJordan:
     def solve(self) -> dict:
         return self.engine.solve()
 
+    def solve_rhs(self, B: np.ndarray, A_rows: Optional[np.ndarray] = None, gen=None, max_refine: int = -1,
+                  tol: float = 1e-15):
+        """Collective, after solve(): A X = B for the n x k block B (an n-vector counts as k = 1),
+        the same full B on every rank, every column refined in fp64 (Engine::solve_rhs_block).  The
+        fp64 matrix comes from ``gen`` = (kind, seed) or from ``A_rows``, this rank's rows of A (in
+        global_row_ids() order) or the full n x n matrix.  Returns (X with B's shape, one info dict
+        per column), the same on every rank."""
+        B = np.asarray(B, dtype=np.float64)
+        b2 = np.ascontiguousarray(B.reshape(self.n, -1))
+        rows = None
+        if gen is None:
+            if A_rows is None:
+                raise ValueError("solve_rhs needs A_rows or gen=(kind, seed) for the fp64 residual")
+            rows = np.asarray(A_rows, dtype=np.float64)
+            if rows.shape == (self.n, self.n) and len(self._rows) != self.n:
+                rows = rows[self._rows]
+            rows = np.ascontiguousarray(rows)
+        else:
+            gen = (str(gen[0]), int(gen[1]))
+        x, infos, _ = self.engine.solve_rhs_block(b2, gen=gen, rows=rows, max_refine=int(max_refine),
+                                                  tol=float(tol))
+        return x.reshape(B.shape), list(infos)
+
     # ---- output
     def local_rows(self) -> np.ndarray:
         return self.engine.download_local_rows()
