@@ -35,6 +35,8 @@
 //                        column j is (j+1) * ones, random -> column j seeded by seed + j, FILE holds
 //                        n * K values, row-major; --json gains per-column arrays, the printed residual
 //                        is the maximum over the columns
+//   --trans              with --rhs: solve A^T x = b from the same inverse (no second inversion) and
+//                        report ||A^T x - b||_inf as "ATx-b residual"; --json gains "trans": true
 //   --out-x FILE         write x (text, or .bin; n x K values, row-major); implies --rhs ones unless
 //                        --rhs is given
 //   --refine K           at most K refinement steps of x with the residual in fp64 (default: 10 for
@@ -97,6 +99,7 @@ static void json_report(const RunConfig& cfg, const RunReport& rep) {
       rhs += buf;
     }
     rhs += "]";
+    if (rep.trans) rhs += ", \"trans\": true";
     if (rep.nrhs > 1) {  // --nrhs K: one entry per column
       auto arr = [&](const char* name, auto&& item) {
         rhs += std::string(", \"") + name + "\": [";
@@ -199,6 +202,7 @@ int main(int argc, char* argv[]) {
       else if (a == "--out") out_file = val("--out");
       else if (a == "--rhs") cfg.rhs = val("--rhs");
       else if (a == "--nrhs") cfg.nrhs = std::atoi(val("--nrhs"));
+      else if (a == "--trans") cfg.trans = true;
       else if (a == "--out-x") x_file = val("--out-x");
       else if (a == "--refine") cfg.refine = std::atoi(val("--refine"));
       else if (a == "--json") json = true;
@@ -279,7 +283,7 @@ int main(int argc, char* argv[]) {
   if (rep.rhs_solved) {  // only with --rhs: the reference has no A x = b mode
     std::printf("solution x:\n");
     for (double v : rep.x_head) std::printf("%.2f\t", v);
-    std::printf("\nAx-b residual: %e\n", rep.rhs_residual);
+    std::printf(rep.trans ? "\nATx-b residual: %e\n" : "\nAx-b residual: %e\n", rep.rhs_residual);
   }
   if (!out_file.empty()) write_matrix_file(out_file, n, rep.inverse.data(), n);
   if (!x_file.empty()) write_vector_file(x_file, n * rep.nrhs, rep.x.data());

@@ -110,6 +110,11 @@ class AsyncHostDevice : public Device {
                            int s) override;
   void copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows, int64_t k,
                         const int32_t* mask, int s) override;
+  void panel_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+                   double* S, int64_t lds, const int32_t* active, int s) override;
+  void axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S, int64_t lds,
+                        double sign, int64_t rows, int64_t k, const int32_t* active, double* colmax, int s) override;
+  void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) override;
 
   // A fence between queues: signalled by the stream that records it, waited on by any stream
   // (of any AsyncHostDevice of this process) or by the host.

@@ -425,10 +425,39 @@ class Device {
   // dst[r*ldd + j] = src[r*lds + j] for r < rows and the columns j < k with mask[j] != 0 (int32[k], device)
   virtual void copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows,
                                 int64_t k, const int32_t* mask, int s) = 0;
+
+  // ---- the transposed block solve (Engine::solve_rhs_block with trans) ----
+  // S[c][j] = sum_r P[r][c] * V[grow(r)][j] for c < L.n and j < k, 1 <= k <= kMaxRhs columns (else
+  // Status::BadArgs): this rank's term of P_full^T V.  The sum runs over this rank's local rows r
+  // whose global row grow(r) = ((r / m) * p + rank) * m + r % m is below n.
+  //   P     this rank's rows of a panel, L.rows x L.npad of dtype dt, leading dimension ldp
+  //   V     the whole block in natural row order, fp64, k columns, leading dimension ldv; only the
+  //         rows this rank owns are read
+  //   S     fp64 in natural order, L.n x k, leading dimension lds; rows >= n are not written
+  //   active  int32[k] (device) or null: a column with active[j] == 0 is not computed, S gets +0.0
+  //           there (so the sum over the ranks stays defined)
+  // F64: fp64 throughout.  F32: V rounded to fp32 on load, the product accumulated in fp32, partial
+  // sums widened and added in fp64 (the arithmetic of panel_rhs).  Never read: P's padding rows, P's
+  // columns >= n, V's rows >= n, V's rows owned by other ranks and the pitch gap of every operand.
+  virtual void panel_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                           int64_t k, double* S, int64_t lds, const int32_t* active, int s) = 0;
+  // Y[r][j] = C_in[r][j] + sign * S[r][j] for r < rows and the columns j < k (1 <= k <= kMaxRhs) with
+  // active[j] != 0 (int32[k], device; null = all), fp64, sign = +1 or -1.  C_in may be null (0) or
+  // alias Y.  colmax (double[k], device, or null): colmax[j] = max |Y[r][j]| over r < rows, NaN kept
+  // as in panel_rhs.  Y and colmax[j] of an inactive column stay untouched.
+  virtual void axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S,
+                                int64_t lds, double sign, int64_t rows, int64_t k, const int32_t* active,
+                                double* colmax, int s) = 0;
+  // out[c] = sum over this rank's real local rows (global row < n) of |X[r][c]| for c < L.n: this
+  // rank's term of the column sums (||A||_1 after a sum over the ranks).  X is L.rows x L.npad of
+  // dtype dt, leading dimension ldx; accumulated in fp64, NaN kept; padding never read.
+  virtual void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) = 0;
 };
 
 // Test probe of Device::panel_rhs, like g_last_gemm_kernel: "host" on the host executor,
 // "rhs<16|32|64>:<f64|f32>:<vec|scalar>:s<split>" on the GPU.
 inline thread_local const char* g_last_rhs_kernel = "";
+// The same of Device::panel_rhs_t: "host", or "rhst<16|32|64>:<f64|f32>:<vec|scalar>:s<split>".
+inline thread_local const char* g_last_rhs_t_kernel = "";
 
 }  // namespace gj

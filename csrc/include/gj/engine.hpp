@@ -206,13 +206,18 @@ class Engine {
   // each matrix once per sweep for all columns; per sweep the host sees the 2k column norms and
   // sends back the column masks).  A column that has stopped is frozen: later sweeps neither
   // compute nor write it.  More than Device::kMaxRhs columns run in groups.
+  // trans: A^T X = B from the same resident inverse.  x_0 = inv(A)^T b, r = b - A^T x and
+  // x += inv(A)^T r are each this rank's term P_loc^T V_loc (Device::panel_rhs_t over its own rows),
+  // summed over the ranks by Comm::allreduce_sum (the same bits on every rank, already in natural
+  // row order: no all-gather, no row reorder) and applied by Device::axpy_cols_masked.  The column
+  // rule is the same; the backward error uses ||A^T||_inf = ||A||_1 (Device::col_abs_sum).
   RhsBlockResult solve_rhs_block(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                  const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
-                                 int64_t ld, int max_refine, double tol);
+                                 int64_t ld, int max_refine, double tol, bool trans = false);
   // The same with B and X in device memory (fp64), e.g. torch CUDA tensors.
   RhsBlockResult solve_rhs_block_device(const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx, int64_t k,
                                         const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
-                                        int64_t ld, int max_refine, double tol);
+                                        int64_t ld, int max_refine, double tol, bool trans = false);
   // Precision of the last residual: true = fp64 (always for fp64 solves; fp32 solves when it fits).
   bool residual_fp64() const { return last_residual_fp64_; }
   // ||A||_inf of the last solve's input (the reference's norm, taken at solve start) and
@@ -289,6 +294,9 @@ class Engine {
   RhsBlockResult solve_rhs_block_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                       bool on_device, const GenSpec* gen, const double* host_rows,
                                       const void* dev_rows, int64_t ld, int max_refine, double tol);
+  RhsBlockResult solve_rhs_block_trans_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
+                                            bool on_device, const GenSpec* gen, const double* host_rows,
+                                            const void* dev_rows, int64_t ld, int max_refine, double tol);
   // GJ_VERIFY (SolveOptions::verify): hash slots of a panel, (d*C + 3d + 1) + 3 (2d + 2) of them:
   //   [chunk c][step j] Rb segment at MAIN's chunk update | pp[j] panel piece at its first consumer
   //   | la[j] look-ahead row segment at the look-ahead update | recs[j] gathered pivot records |

@@ -111,6 +111,11 @@ class HipDevice : public Device {
                            int s) override;
   void copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows, int64_t k,
                         const int32_t* mask, int s) override;
+  void panel_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+                   double* S, int64_t lds, const int32_t* active, int s) override;
+  void axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S, int64_t lds,
+                        double sign, int64_t rows, int64_t k, const int32_t* active, double* colmax, int s) override;
+  void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) override;
 
  private:
   void* scratch(size_t bytes, int slot);
@@ -121,8 +126,8 @@ class HipDevice : public Device {
   int bi_hint_ = -1;  // set_block_inverse_hint
   int tile_hint_ = 0;  // set_gemm_tile_hint
   std::vector<void*> events_;
-  void* scratch_[3] = {nullptr, nullptr, nullptr};  // 2: panel_rhs K-slice partials
-  size_t scratch_sz_[3] = {0, 0, 0};
+  void* scratch_[4] = {nullptr, nullptr, nullptr, nullptr};  // 2, 3: panel_rhs / panel_rhs_t slice partials
+  size_t scratch_sz_[4] = {0, 0, 0, 0};
 };
 
 }  // namespace gj

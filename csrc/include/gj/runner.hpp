@@ -38,6 +38,9 @@ struct RunConfig {
   // block path (Engine::solve_rhs_block); "ones": column j is (j + 1) * ones, "random": column j is
   // seeded by gen.seed + j, a file holds n * nrhs values, row-major.
   int nrhs = 1;
+  // A^T x = b from the same inverse (Engine::solve_rhs_block with trans, at any nrhs >= 1); the
+  // reported residual is then ||A^T x - b||_inf
+  bool trans = false;
   bool keep_solution = false;         // return x in RunReport::x
   // iterative refinement of x with the residual in fp64 (Engine::solve_rhs): at most `refine`
   // steps (-1 = auto: 10 for fp32 solves, 2 for fp64), stop at backward error <= refine_tol
@@ -75,6 +78,7 @@ struct RunReport {
   // maxima over the columns, rhs_converged holds when every column converged, rhs_history is the
   // history of the column with the largest residual, x_head the head of column 0
   int nrhs = 1;
+  bool trans = false;               // the right-hand sides were solved against A^T
   std::vector<RhsResult> rhs_cols;
   // race_check: unordered conflicting accesses found (total, the first distinct ones described),
   // ops checked

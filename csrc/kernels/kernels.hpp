@@ -143,5 +143,20 @@ void copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, 
 void set_rhs_splitk(int s);
 const char* last_rhs_kernel();
 
+// panel_rhs_t.hip: Device::panel_rhs_t / axpy_cols_masked / col_abs_sum.  scratch: the row-slice
+// partials, panel_rhs_t_scratch_bytes(...) bytes (for the split and load width the launch will use).
+size_t panel_rhs_t_scratch_bytes(DType dt, const void* P, int64_t ldp, const Layout& L, int64_t k);
+void panel_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+                 double* S, int64_t lds, const int32_t* active, void* scratch, hipStream_t s);
+void axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S, int64_t lds,
+                      double sign, int64_t rows, int64_t k, const int32_t* active, double* colmax, hipStream_t s);
+void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, hipStream_t s);
+// Test hooks: row split of the following panel_rhs_t launches (0 = auto, s >= 1 forces s; a launch
+// never runs an empty slice, so at most ceil(real rows / 4) take part), and the name of this thread's
+// last panel_rhs_t launch, "rhst<16|32|64>:<f64|f32>:<vec|scalar>:s<split>" ("host" on the host
+// executor).  Separate from set_rhs_splitk / last_rhs_kernel.
+void set_rhs_t_split(int s);
+const char* last_rhs_t_kernel();
+
 }  // namespace kern
 }  // namespace gj

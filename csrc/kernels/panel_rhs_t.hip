@@ -1,0 +1,387 @@
+// Kernels of the transposed block solve (Device::panel_rhs_t, axpy_cols_masked, col_abs_sum;
+// Engine::solve_rhs_block with trans), gfx950.
+//
+// panel_rhs_t: S = P^T V_loc with P this rank's rows of a tall panel (rows x n of fp64 / fp32) and
+// V a skinny fp64 block in natural row order (k <= 64 columns), of which local row r uses the row
+// grow(r) = ((r / m) p + rank) m + r % m.  The reduction runs over the local rows, the output has
+// one row per column of P.  P is the memory-bound operand: every element is read exactly once per
+// launch, straight from HBM into MFMA A-operand registers.  For D = P^T-fragment * V-fragment the
+// 16 lanes of one MFMA K index hold 16 consecutive columns of one row of P, so a row-major P is
+// read in whole contiguous segments (16-byte loads where the rows are 16-byte aligned, element
+// loads otherwise); V stays in L2 and reaches the waves through LDS, once per workgroup.
+//
+//   pass 1  grid (column tiles of 64 W, S row slices), W = elements per load: a wave owns 16 W
+//           columns of P (W column fragments) and NF = 1 | 2 | 4 fragments of 16 columns of V
+//           (v_mfma_{f64,f32}_16x16x4), walks its slice of the rows and stores the partial product,
+//           widened to fp64, to part[slice][column of P][column of V]
+//   pass 2  S = sum_{slice} part in slice order (+0.0 for an inactive column)
+//
+// The reduction dimension is the local rows, so a small panel has few column tiles and the rows are
+// split over S workgroups (auto, or set_rhs_t_split).  The slices are summed by pass 2 in a fixed
+// order: the result is bit-identical from run to run, no floating-point value is accumulated with
+// atomics.
+//
+// Masks, not assumptions: padding rows (global row >= n; they are the tail of the local rows, only
+// the last global block row is short), columns >= n of P, columns >= k and inactive columns of V
+// are never loaded (their operand is 0), whatever m, n, p, the rank and the leading dimensions are.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+
+#include "kernels.hpp"
+
+namespace gj {
+namespace kern {
+
+namespace {
+
+constexpr int kRtWaves = 4;       // waves per workgroup, each on its own columns of P
+constexpr int kRtKC = 32;         // local rows per LDS stage of V
+constexpr int kRtMaxSplit = 64;
+
+template <typename T>
+struct RtMfma;
+template <>
+struct RtMfma<double> {
+  typedef double acc_t __attribute__((ext_vector_type(4)));
+  typedef double vec_t __attribute__((ext_vector_type(2)));
+  static constexpr int W = 2;  // elements of a 16-byte load
+  // LDS row pitch = 16 (mod 32) elements: the 4 K lanes of a B-fragment read sit on consecutive
+  // rows, 128 (mod 256) bytes apart
+  static constexpr int pad(int kw) { return kw == 16 ? 0 : 16; }
+  static __device__ __forceinline__ acc_t op(double a, double b, acc_t c) {
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ int row(int lane, int q) { return (lane >> 4) + 4 * q; }
+};
+template <>
+struct RtMfma<float> {
+  typedef float acc_t __attribute__((ext_vector_type(4)));
+  typedef float vec_t __attribute__((ext_vector_type(4)));
+  static constexpr int W = 4;
+  // pitch = 16 (mod 64) elements: consecutive rows 64 (mod 256) bytes apart
+  static constexpr int pad(int kw) { return kw == 16 ? 0 : kw == 32 ? 48 : 16; }
+  static __device__ __forceinline__ acc_t op(float a, float b, acc_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ int row(int lane, int q) { return 4 * (lane >> 4) + q; }
+};
+
+// the order of non-negative doubles as integers, NaN (either sign) above +Inf: misc.hip nonneg_key
+__device__ __forceinline__ unsigned long long rt_key(double v) {
+  v = (v >= 0.0) ? fabs(v) : __longlong_as_double(0x7ff8000000000000ll);
+  return (unsigned long long)__double_as_longlong(v);
+}
+
+// Pass 1.  W = elements each lane loads per row (1: element loads, any alignment; RtMfma<T>::W: one
+// 16-byte load, rows 16-byte aligned).  A K step covers 4 local rows: lane (i = lane % 16,
+// g = lane / 16) holds P[row + g][c0 + i W + j], j < W, and the j-th MFMA of the step produces the
+// output rows {c0 + i W + j : i < 16} -- W interleaved column fragments from one load.
+//
+// V goes through LDS in chunks of kRtKC local rows, picked by the row map and converted to T once
+// per workgroup (every wave of a workgroup needs the same rows of V).  Two buffers, one barrier per
+// chunk: chunk c + 1 is fetched into registers before chunk c is multiplied and written to the other
+// buffer after it.  `real` = this rank's real local rows (global row < n), a prefix of its rows.
+template <typename T, int NF, int W>
+__global__ __launch_bounds__(64 * kRtWaves) void panel_rhs_t_kernel(
+    const T* __restrict__ P, int64_t ldp, int64_t real, int64_t n, uint32_t m, int64_t p, int64_t rk,
+    const double* __restrict__ V, int64_t ldv, int k, const int32_t* __restrict__ active,
+    double* __restrict__ part, int64_t cols_pad, int64_t rchunk) {
+  using MF = RtMfma<T>;
+  constexpr int KW = 16 * NF;
+  constexpr int NT = 64 * kRtWaves;
+  constexpr int LDK = KW + MF::pad(KW);      // LDS row pitch (elements)
+  constexpr int VPT = kRtKC * KW / NT;       // elements of a V chunk per thread (column fixed)
+  constexpr int STEPS = kRtKC / 4;           // K steps per chunk
+  static_assert(NT % KW == 0 && (kRtKC * KW) % NT == 0 && kRtKC % 4 == 0, "chunk shape");
+  __shared__ T vs[2][kRtKC][LDK];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = lane & 15, g = lane >> 4;
+
+  const int64_t cbase = ((int64_t)blockIdx.x * kRtWaves + wave) * (16 * W);  // this wave's columns of P
+  const int64_t c0 = cbase + i * W;                                          // this lane's
+  const bool cvec = c0 + W <= n;
+  const int64_t rbeg = (int64_t)blockIdx.y * rchunk;
+  const int64_t rend = rbeg + rchunk < real ? rbeg + rchunk : real;
+
+  // staging: this thread's column of V and its rows of a chunk (row vr0 + q * (NT / KW))
+  const int vc = threadIdx.x % KW, vr0 = threadIdx.x / KW;
+  const bool vcv = vc < k && (!active || active[vc] != 0);
+  double vreg[VPT];
+  auto fetch = [&](int64_t rb) {
+#pragma unroll
+    for (int q = 0; q < VPT; ++q) {
+      const int64_t r = rb + vr0 + q * (NT / KW);
+      double v = 0.0;
+      if (vcv && r < rend) {
+        const uint32_t b = (uint32_t)r / m, e = (uint32_t)r - b * m;  // local rows < 2^31
+        v = V[(((int64_t)b * p + rk) * m + e) * ldv + vc];
+      }
+      vreg[q] = v;
+    }
+  };
+  auto stage = [&](int buf) {
+#pragma unroll
+    for (int q = 0; q < VPT; ++q) vs[buf][vr0 + q * (NT / KW)][vc] = (T)vreg[q];
+  };
+
+  typename MF::acc_t acc[W][NF];
+#pragma unroll
+  for (int j = 0; j < W; ++j)
+#pragma unroll
+    for (int nf = 0; nf < NF; ++nf) acc[j][nf] = typename MF::acc_t{0, 0, 0, 0};
+
+  fetch(rbeg);
+  stage(0);
+  __syncthreads();
+  int buf = 0;
+  for (int64_t rb = rbeg; rb < rend; rb += kRtKC, buf ^= 1) {
+    const bool more = rb + kRtKC < rend;  // uniform over the workgroup
+    if (more) fetch(rb + kRtKC);
+    T a[STEPS][W];
+#pragma unroll
+    for (int st = 0; st < STEPS; ++st) {
+      const int64_t r = rb + st * 4 + g;
+      const T* src = P + r * ldp + c0;
+      if (W > 1 && cvec && r < rend) {
+        const typename MF::vec_t v = *reinterpret_cast<const typename MF::vec_t*>(src);
+#pragma unroll
+        for (int j = 0; j < W; ++j) a[st][j] = v[j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < W; ++j) a[st][j] = (r < rend && c0 + j < n) ? src[j] : T(0);
+      }
+    }
+#pragma unroll
+    for (int st = 0; st < STEPS; ++st) {
+      T b[NF];
+#pragma unroll
+      for (int nf = 0; nf < NF; ++nf) b[nf] = vs[buf][st * 4 + g][nf * 16 + i];
+#pragma unroll
+      for (int j = 0; j < W; ++j)
+#pragma unroll
+        for (int nf = 0; nf < NF; ++nf) acc[j][nf] = MF::op(a[st][j], b[nf], acc[j][nf]);
+    }
+    if (more) stage(buf ^ 1);
+    __syncthreads();
+  }
+
+  // partial product of this row slice, widened: cols_pad is a whole number of tiles, no mask
+  double* out = part + ((int64_t)blockIdx.y * cols_pad + cbase) * KW;
+#pragma unroll
+  for (int j = 0; j < W; ++j)
+#pragma unroll
+    for (int nf = 0; nf < NF; ++nf)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        out[(int64_t)(MF::row(lane, q) * W + j) * KW + nf * 16 + i] = (double)acc[j][nf][q];
+}
+
+// Pass 2: one thread per element of S (c < n, j < k).
+template <int KW>
+__global__ __launch_bounds__(256) void panel_rhs_t_reduce(const double* __restrict__ part, int S, int64_t cols_pad,
+                                                          int64_t n, int k, double* __restrict__ out, int64_t lds,
+                                                          const int32_t* __restrict__ active) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t c = t / KW;
+  const int j = (int)(t % KW);
+  if (c >= n || j >= k) return;
+  double sum = 0.0;
+  if (!active || active[j] != 0)
+    for (int s = 0; s < S; ++s) sum += part[((int64_t)s * cols_pad + c) * KW + j];
+  out[c * lds + j] = sum;
+}
+
+// colmax of the active columns starts from 0 (the integer key of +0.0)
+__global__ void axpy_cols_init_kernel(unsigned long long* colmax, int k, const int32_t* __restrict__ active) {
+  const int j = threadIdx.x;
+  if (j < k && (!active || active[j] != 0)) colmax[j] = 0ull;
+}
+
+// Y = C_in + sign S on the active columns, and their maxima.  A workgroup covers rpb rows x KW columns
+// (thread = column tid % KW, row group tid / KW).
+template <int KW>
+__global__ __launch_bounds__(256) void axpy_cols_masked_kernel(double* Y, int64_t ldy, const double* C_in,
+                                                               int64_t ldc, const double* __restrict__ S,
+                                                               int64_t lds, double sign, int64_t rows, int k,
+                                                               const int32_t* __restrict__ active,
+                                                               unsigned long long* colmax, int rpb) {
+  constexpr int RG = 256 / KW;
+  const int c = threadIdx.x % KW, rs = threadIdx.x / KW;
+  const bool on = c < k && (!active || active[c] != 0);
+  const int64_t base = (int64_t)blockIdx.x * rpb;
+  const int64_t end = base + rpb < rows ? base + rpb : rows;
+  unsigned long long key = 0ull;
+  if (on)
+    for (int64_t r = base + rs; r < end; r += RG) {
+      const double y = (C_in ? C_in[r * ldc + c] : 0.0) + sign * S[r * lds + c];
+      Y[r * ldy + c] = y;
+      const unsigned long long kk = rt_key(fabs(y));
+      key = kk > key ? kk : key;
+    }
+  if (!colmax) return;
+  __shared__ unsigned long long sh[256];
+  sh[threadIdx.x] = key;
+  __syncthreads();
+  if (rs == 0 && on) {
+#pragma unroll
+    for (int q = 1; q < RG; ++q) key = sh[q * KW + c] > key ? sh[q * KW + c] : key;
+    atomicMax(colmax + c, key);  // an integer maximum: the same bits in any order
+  }
+}
+
+// out[c] = sum over the real local rows of |X[r][c]|: a workgroup covers 64 columns, its 4 row
+// groups walk the rows 4 apart and are summed in a fixed order.
+template <typename T>
+__global__ __launch_bounds__(256) void col_abs_sum_kernel(const T* __restrict__ X, int64_t ldx, int64_t real,
+                                                          int64_t n, double* __restrict__ out) {
+  const int cl = threadIdx.x & 63, rs = threadIdx.x >> 6;
+  const int64_t c = (int64_t)blockIdx.x * 64 + cl;
+  double sum = 0.0;
+  if (c < n)
+    for (int64_t r = rs; r < real; r += 4) sum += fabs((double)X[r * ldx + c]);
+  __shared__ double sh[4][64];
+  sh[rs][cl] = sum;
+  __syncthreads();
+  if (rs == 0 && c < n) out[c] = ((sh[0][cl] + sh[1][cl]) + sh[2][cl]) + sh[3][cl];
+}
+
+int g_rt_split = 0;  // set_rhs_t_split
+thread_local char g_rt_name[48] = "";
+
+int rt_num_cus() {
+  static int ncu = 0;
+  if (ncu == 0) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+      ncu = v;
+    else
+      ncu = 256;
+  }
+  return ncu;
+}
+
+// this rank's real local rows: all but the padding of the last global block row
+int64_t real_rows(const Layout& L) {
+  int64_t r = 0;
+  for (int64_t b = 0; b < L.nblk; ++b) r += std::max<int64_t>(0, std::min<int64_t>(L.m, L.n - L.global_block(b) * L.m));
+  return r;
+}
+
+struct RtPlan {
+  int64_t tiles, cols_pad, rchunk, real;
+  int S, W;
+  bool vec;
+};
+
+RtPlan rt_plan(DType dt, const void* P, int64_t ldp, const Layout& L) {
+  RtPlan pl;
+  const size_t es = dtype_size(dt);
+  // 16-byte loads of P need 16-byte aligned rows; a lane's columns start on a multiple of W
+  pl.vec = reinterpret_cast<uintptr_t>(P) % 16 == 0 && ((size_t)ldp * es) % 16 == 0;
+  pl.W = pl.vec ? (int)(16 / es) : 1;
+  const int64_t tw = 16 * pl.W * kRtWaves;
+  pl.tiles = std::max<int64_t>((L.n + tw - 1) / tw, 1);
+  pl.cols_pad = pl.tiles * tw;
+  pl.real = real_rows(L);
+  int64_t S = g_rt_split;
+  if (S <= 0) {
+    // memory-bound: about two workgroups per CU keep HBM busy; a slice of at least 128 rows
+    S = (2 * (int64_t)rt_num_cus() + pl.tiles - 1) / pl.tiles;
+    S = std::min<int64_t>(S, std::max<int64_t>(pl.real / 128, 1));
+  }
+  S = std::max<int64_t>(1, std::min<int64_t>(S, kRtMaxSplit));
+  // slices are whole K steps of 4 rows
+  pl.rchunk = std::max<int64_t>((((pl.real + S - 1) / S + 3) / 4) * 4, 4);
+  pl.S = (int)std::max<int64_t>((pl.real + pl.rchunk - 1) / pl.rchunk, 1);  // no empty slice
+  return pl;
+}
+
+template <typename T, int NF>
+void launch_rt(const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int k,
+               const int32_t* active, double* part, const RtPlan& pl, hipStream_t s) {
+  const dim3 grid((unsigned)pl.tiles, (unsigned)pl.S), block(64 * kRtWaves);
+  if (pl.vec)
+    hipLaunchKernelGGL((panel_rhs_t_kernel<T, NF, RtMfma<T>::W>), grid, block, 0, s, static_cast<const T*>(P), ldp,
+                       pl.real, L.n, (uint32_t)L.m, L.p, L.k, V, ldv, k, active, part, pl.cols_pad, pl.rchunk);
+  else
+    hipLaunchKernelGGL((panel_rhs_t_kernel<T, NF, 1>), grid, block, 0, s, static_cast<const T*>(P), ldp, pl.real,
+                       L.n, (uint32_t)L.m, L.p, L.k, V, ldv, k, active, part, pl.cols_pad, pl.rchunk);
+}
+
+template <int KW>
+void launch_rt_reduce(const double* part, const RtPlan& pl, const Layout& L, int k, double* S, int64_t lds,
+                      const int32_t* active, hipStream_t s) {
+  const int64_t work = L.n * KW;
+  hipLaunchKernelGGL((panel_rhs_t_reduce<KW>), dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, part, pl.S,
+                     pl.cols_pad, L.n, k, S, lds, active);
+}
+
+}  // namespace
+
+void set_rhs_t_split(int s) { g_rt_split = s < 0 ? 0 : s; }
+const char* last_rhs_t_kernel() { return g_last_rhs_t_kernel; }
+
+size_t panel_rhs_t_scratch_bytes(DType dt, const void* P, int64_t ldp, const Layout& L, int64_t k) {
+  const RtPlan pl = rt_plan(dt, P, ldp, L);
+  const int kw = k <= 16 ? 16 : k <= 32 ? 32 : 64;
+  return sizeof(double) * (size_t)pl.S * (size_t)pl.cols_pad * kw;
+}
+
+void panel_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+                 double* S, int64_t lds, const int32_t* active, void* scratch, hipStream_t s) {
+  if (L.n <= 0) return;
+  const RtPlan pl = rt_plan(dt, P, ldp, L);
+  const int nf = k <= 16 ? 1 : k <= 32 ? 2 : 4;
+  double* part = static_cast<double*>(scratch);
+  std::snprintf(g_rt_name, sizeof(g_rt_name), "rhst%d:%s:%s:s%d", 16 * nf, dt == DType::F64 ? "f64" : "f32",
+                pl.vec ? "vec" : "scalar", pl.S);
+  g_last_rhs_t_kernel = g_rt_name;
+#define GJ_RT_LAUNCH(T)                                                            \
+  do {                                                                             \
+    if (nf == 1) launch_rt<T, 1>(P, ldp, L, V, ldv, (int)k, active, part, pl, s);   \
+    else if (nf == 2) launch_rt<T, 2>(P, ldp, L, V, ldv, (int)k, active, part, pl, s); \
+    else launch_rt<T, 4>(P, ldp, L, V, ldv, (int)k, active, part, pl, s);           \
+  } while (0)
+  if (dt == DType::F64) GJ_RT_LAUNCH(double);
+  else GJ_RT_LAUNCH(float);
+#undef GJ_RT_LAUNCH
+  if (nf == 1) launch_rt_reduce<16>(part, pl, L, (int)k, S, lds, active, s);
+  else if (nf == 2) launch_rt_reduce<32>(part, pl, L, (int)k, S, lds, active, s);
+  else launch_rt_reduce<64>(part, pl, L, (int)k, S, lds, active, s);
+}
+
+void axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S, int64_t lds,
+                      double sign, int64_t rows, int64_t k, const int32_t* active, double* colmax, hipStream_t s) {
+  unsigned long long* cm = reinterpret_cast<unsigned long long*>(colmax);
+  if (cm) hipLaunchKernelGGL(axpy_cols_init_kernel, dim3(1), dim3(64), 0, s, cm, (int)k, active);
+  if (rows <= 0) return;
+#define GJ_AXPY_LAUNCH(KW)                                                                                    \
+  do {                                                                                                        \
+    const int rpb = 4 * (256 / KW);                                                                           \
+    hipLaunchKernelGGL((axpy_cols_masked_kernel<KW>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, Y, \
+                       ldy, C_in, ldc, S, lds, sign, rows, (int)k, active, cm, rpb);                           \
+  } while (0)
+  if (k <= 16) GJ_AXPY_LAUNCH(16);
+  else if (k <= 32) GJ_AXPY_LAUNCH(32);
+  else GJ_AXPY_LAUNCH(64);
+#undef GJ_AXPY_LAUNCH
+}
+
+void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, hipStream_t s) {
+  if (L.n <= 0) return;
+  const unsigned grid = (unsigned)((L.n + 63) / 64);
+  const int64_t real = real_rows(L);
+  if (dt == DType::F64)
+    hipLaunchKernelGGL(col_abs_sum_kernel<double>, dim3(grid), dim3(256), 0, s, static_cast<const double*>(X), ldx,
+                       real, L.n, out);
+  else
+    hipLaunchKernelGGL(col_abs_sum_kernel<float>, dim3(grid), dim3(256), 0, s, static_cast<const float*>(X), ldx,
+                       real, L.n, out);
+}
+
+}  // namespace kern
+}  // namespace gj

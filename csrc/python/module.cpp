@@ -226,6 +226,11 @@ PYBIND11_MODULE(_C, mod) {
   mod.def("last_rhs_kernel", [] { return std::string(kern::last_rhs_kernel()); },
           "test probe: 'rhs<16|32|64>:<f64|f32>:<vec|scalar>:s<split>' of this thread's last Device.panel_rhs "
           "('host' on the host executor)");
+  mod.def("set_rhs_t_split", [](int v) { kern::set_rhs_t_split(v); },
+          "test hook: row split of the following Device.panel_rhs_t launches on the GPU (0 = auto, s >= 1 forces s)");
+  mod.def("last_rhs_t_kernel", [] { return std::string(kern::last_rhs_t_kernel()); },
+          "test probe: 'rhst<16|32|64>:<f64|f32>:<vec|scalar>:s<split>' of this thread's last Device.panel_rhs_t "
+          "('host' on the host executor)");
   mod.def("set_lat_glds", [](bool on) { kern::set_lat_glds(on ? 1 : 0); },
           "every latency GEMM of >= 1024 rows on the LDS-DMA kernel (tests; the engine sets it per launch)");
 
@@ -447,6 +452,43 @@ PYBIND11_MODULE(_C, mod) {
              d.sync_stream(S_MAIN);
              return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
            })
+      // The same timing of panel_rhs_t (S = P^T V, every column active) and of the K-major GEMM it is
+      // measured against (C = At^T B with At = P: M = n, K = the rows of P).
+      .def("time_panel_rhs_t",
+           [lay](Device& d, const std::string& dt, U P, int64_t ldp, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U V, int64_t ldv, int64_t ncols, U S, int64_t lds, int reps) {
+             py::gil_scoped_release rel;
+             const Layout L = lay(n, m, p, k);
+             const DType t = parse_dtype(dt);
+             auto run = [&] {
+               d.panel_rhs_t(t, (const void*)P, ldp, L, (const double*)V, ldv, ncols, (double*)S, lds, nullptr,
+                             S_MAIN);
+             };
+             run();
+             const int e0 = d.create_event(true), e1 = d.create_event(true);
+             d.record(e0, S_MAIN);
+             for (int i = 0; i < reps; ++i) run();
+             d.record(e1, S_MAIN);
+             d.sync_stream(S_MAIN);
+             return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
+           })
+      .def("time_gemm_store_kmajor",
+           [](Device& d, const std::string& dt, int64_t M, int64_t N, int64_t K, U A, int64_t lda, U B, int64_t ldb,
+              U C, int64_t ldc, int reps) {
+             py::gil_scoped_release rel;
+             const DType t = parse_dtype(dt);
+             auto run = [&] {
+               d.gemm(t, GemmOp::Store, ALayout::KMajor, M, N, K, (const void*)A, lda, (const void*)B, ldb, (void*)C,
+                      ldc, S_MAIN);
+             };
+             run();
+             const int e0 = d.create_event(true), e1 = d.create_event(true);
+             d.record(e0, S_MAIN);
+             for (int i = 0; i < reps; ++i) run();
+             d.record(e1, S_MAIN);
+             d.sync_stream(S_MAIN);
+             return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
+           })
       .def("time_gemm_store",
            [](Device& d, const std::string& dt, int64_t M, int64_t N, int64_t K, U A, int64_t lda, U B, int64_t ldb,
               U C, int64_t ldc, int reps) {
@@ -555,6 +597,34 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("dt"), py::arg("P"), py::arg("ldp"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"),
            py::arg("V"), py::arg("ldv"), py::arg("ncols"), py::arg("C_in"), py::arg("ldc"), py::arg("Y"),
            py::arg("ldy"), py::arg("sign"), py::arg("active") = U(0), py::arg("colmax") = U(0))
+      // S = P^T V over this rank's real rows (its term of the transposed product); 0 = a null pointer
+      .def("panel_rhs_t",
+           [lay](Device& d, const std::string& dt, U P, int64_t ldp, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U V, int64_t ldv, int64_t ncols, U S, int64_t lds, U active) {
+             py::gil_scoped_release rel;
+             d.panel_rhs_t(parse_dtype(dt), (const void*)P, ldp, lay(n, m, p, k), (const double*)V, ldv, ncols,
+                           (double*)S, lds, (const int32_t*)active, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("dt"), py::arg("P"), py::arg("ldp"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"),
+           py::arg("V"), py::arg("ldv"), py::arg("ncols"), py::arg("S"), py::arg("lds"), py::arg("active") = U(0))
+      .def("axpy_cols_masked",
+           [](Device& d, U Y, int64_t ldy, U C_in, int64_t ldc, U S, int64_t lds, double sign, int64_t rows,
+              int64_t ncols, U active, U colmax) {
+             py::gil_scoped_release rel;
+             d.axpy_cols_masked((double*)Y, ldy, (const double*)C_in, ldc, (const double*)S, lds, sign, rows, ncols,
+                                (const int32_t*)active, (double*)colmax, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("Y"), py::arg("ldy"), py::arg("C_in"), py::arg("ldc"), py::arg("S"), py::arg("lds"),
+           py::arg("sign"), py::arg("rows"), py::arg("ncols"), py::arg("active") = U(0), py::arg("colmax") = U(0))
+      .def("col_abs_sum",
+           [lay](Device& d, const std::string& dt, U X, int64_t ldx, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U out) {
+             py::gil_scoped_release rel;
+             d.col_abs_sum(parse_dtype(dt), (const void*)X, ldx, lay(n, m, p, k), (double*)out, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
       .def("gather_rows_natural",
            [lay](Device& d, U dst, int64_t ldd, U src, int64_t lds, int64_t n, int64_t m, int64_t p, int64_t ncols) {
              d.gather_rows_natural((double*)dst, ldd, (const double*)src, lds, lay(n, m, p, 0), ncols, S_MAIN);
@@ -850,7 +920,7 @@ PYBIND11_MODULE(_C, mod) {
       .def("solve_rhs_block",
            [](PyEngine& e, py::object B, py::object gen, py::object rows, uintptr_t rows_f64, int64_t ld,
               uintptr_t b_dev, int64_t ldb, uintptr_t x_dev, int64_t ldx, int64_t ncols, int max_refine,
-              double tol) {
+              double tol, bool trans) {
              const int64_t n = e.eng->layout().n;
              if (max_refine < 0) max_refine = e.eng->options().dtype == DType::F64 ? 2 : 10;
              GenSpec g;
@@ -881,7 +951,8 @@ PYBIND11_MODULE(_C, mod) {
                py::gil_scoped_release rel;
                br = e.eng->solve_rhs_block_device(reinterpret_cast<const double*>(b_dev), ldb,
                                                   reinterpret_cast<double*>(x_dev), ldx, ncols, gp, hrp,
-                                                  reinterpret_cast<const void*>(rows_f64), ldr, max_refine, tol);
+                                                  reinterpret_cast<const void*>(rows_f64), ldr, max_refine, tol,
+                                                  trans);
              } else {
                auto b = B.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
                if (b.ndim() != 2 || b.shape(0) != n || b.shape(1) < 1)
@@ -891,7 +962,7 @@ PYBIND11_MODULE(_C, mod) {
                {
                  py::gil_scoped_release rel;
                  br = e.eng->solve_rhs_block(b.data(), k, x.mutable_data(), k, k, gp, hrp,
-                                             reinterpret_cast<const void*>(rows_f64), ldr, max_refine, tol);
+                                             reinterpret_cast<const void*>(rows_f64), ldr, max_refine, tol, trans);
                }
                xo = x;
              }
@@ -905,11 +976,31 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("B") = py::none(), py::arg("gen") = py::none(), py::arg("rows") = py::none(),
            py::arg("rows_f64") = 0, py::arg("ld") = 0, py::arg("b_dev") = 0, py::arg("ldb") = 0,
            py::arg("x_dev") = 0, py::arg("ldx") = 0, py::arg("ncols") = 0, py::arg("max_refine") = -1,
-           py::arg("tol") = 1e-15,
-           "A X = B after solve() for a block of right-hand sides (Engine::solve_rhs_block): every column refined "
+           py::arg("tol") = 1e-15, py::arg("trans") = false,
+           "A X = B (trans: A^T X = B) after solve() for a block of right-hand sides (Engine::solve_rhs_block): every "
+           "column refined "
            "in fp64 against A given as gen=(kind, seed), rows (this rank's fp64 rows, host) or rows_f64 / ld (an "
            "fp64 device array).  B: an (n, k) host array -> returns (X, infos, meta); or b_dev / x_dev device "
            "pointers (fp64, n x ncols) -> X is written in place and returned as None")
+      .def("solve_rhs_rows",
+           [](PyEngine& e, py::array_t<double, py::array::c_style | py::array::forcecast> b,
+              py::array_t<double, py::array::c_style | py::array::forcecast> rows, int max_refine, double tol) {
+             const int64_t n = e.eng->layout().n;
+             if (b.ndim() != 1 || b.shape(0) != n) throw std::invalid_argument("b must be an n-vector");
+             if (rows.ndim() != 2 || rows.shape(0) != e.eng->real_local_rows() || rows.shape(1) != n)
+               throw std::invalid_argument("rows must be (real_rows, n) float64");
+             if (max_refine < 0) max_refine = e.eng->options().dtype == DType::F64 ? 2 : 10;
+             py::array_t<double> x(n);
+             RhsResult rr;
+             {
+               py::gil_scoped_release rel;
+               rr = e.eng->solve_rhs(b.data(), x.mutable_data(), nullptr, rows.data(), n, max_refine, tol);
+             }
+             return py::make_tuple(x, rhs_info(rr));
+           },
+           py::arg("b"), py::arg("rows"), py::arg("max_refine") = -1, py::arg("tol") = 1e-15,
+           "A x = b after solve(): x = inv(A) b, refined in fp64 against this rank's fp64 rows of A on the host "
+           "(Engine::solve_rhs); returns (x, info)")
       .def("solve_rhs_generated",
            [](PyEngine& e, const std::string& kind, uint64_t seed,
               py::array_t<double, py::array::c_style | py::array::forcecast> b, int max_refine, double tol) {
@@ -1050,6 +1141,7 @@ PYBIND11_MODULE(_C, mod) {
     if (d.contains("rhs")) c.rhs = d["rhs"].cast<std::string>();
     if (d.contains("nrhs")) c.nrhs = d["nrhs"].cast<int>();
     if (c.nrhs < 1) throw std::invalid_argument("nrhs must be >= 1");
+    if (d.contains("trans")) c.trans = d["trans"].cast<bool>();
     if (d.contains("keep_solution")) c.keep_solution = d["keep_solution"].cast<bool>();
     if (d.contains("comm_timeout_s")) c.solve.comm_timeout_s = d["comm_timeout_s"].cast<double>();
     if (d.contains("residual")) {
@@ -1111,7 +1203,8 @@ PYBIND11_MODULE(_C, mod) {
       o["axb_backward_error"] = r.rhs_backward_error;
       o["x_head"] = r.x_head;
       if (c.keep_solution) o["x"] = to_array(r.x, c.n, r.nrhs);
-      if (r.nrhs > 1) {
+      if (r.trans) o["trans"] = true;
+      if (r.nrhs > 1 || r.trans) {
         py::list cols;
         for (const RhsResult& rc : r.rhs_cols) cols.append(rhs_info(rc));
         o["axb_columns"] = cols;

@@ -352,4 +352,20 @@ void AsyncHostDevice::copy_cols_masked(double* dst, int64_t ldd, const double* s
   enqueue(s, [=] { inner_.copy_cols_masked(dst, ldd, src, lds, rows, k, mask, s); });
 }
 
+void AsyncHostDevice::panel_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V,
+                                  int64_t ldv, int64_t k, double* S, int64_t lds, const int32_t* active, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_rhs_t: 1 <= k <= 64 columns");
+  g_last_rhs_t_kernel = "host";
+  enqueue(s, [=] { inner_.panel_rhs_t(dt, P, ldp, L, V, ldv, k, S, lds, active, s); });
+}
+void AsyncHostDevice::axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S,
+                                       int64_t lds, double sign, int64_t rows, int64_t k, const int32_t* active,
+                                       double* colmax, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "axpy_cols_masked: 1 <= k <= 64 columns");
+  enqueue(s, [=] { inner_.axpy_cols_masked(Y, ldy, C_in, ldc, S, lds, sign, rows, k, active, colmax, s); });
+}
+void AsyncHostDevice::col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) {
+  enqueue(s, [=] { inner_.col_abs_sum(dt, X, ldx, L, out, s); });
+}
+
 }  // namespace gj

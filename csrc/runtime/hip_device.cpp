@@ -422,4 +422,23 @@ void HipDevice::copy_cols_masked(double* dst, int64_t ldd, const double* src, in
   check_launch();
 }
 
+void HipDevice::panel_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                            int64_t k, double* S, int64_t lds, const int32_t* active, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_rhs_t: 1 <= k <= 64 columns");
+  void* part = scratch(kern::panel_rhs_t_scratch_bytes(dt, P, ldp, L, k), 3);
+  kern::panel_rhs_t(dt, P, ldp, L, V, ldv, k, S, lds, active, part, hs(streams_[s]));
+  check_launch();
+}
+void HipDevice::axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S,
+                                 int64_t lds, double sign, int64_t rows, int64_t k, const int32_t* active,
+                                 double* colmax, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "axpy_cols_masked: 1 <= k <= 64 columns");
+  kern::axpy_cols_masked(Y, ldy, C_in, ldc, S, lds, sign, rows, k, active, colmax, hs(streams_[s]));
+  check_launch();
+}
+void HipDevice::col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) {
+  kern::col_abs_sum(dt, X, ldx, L, out, hs(streams_[s]));
+  check_launch();
+}
+
 }  // namespace gj

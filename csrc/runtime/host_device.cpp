@@ -604,4 +604,58 @@ void HostDevice::copy_cols_masked(double* dst, int64_t ldd, const double* src, i
       if (mask[j] != 0) dst[r * ldd + j] = src[r * lds + j];
 }
 
+void HostDevice::panel_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                             int64_t k, double* S, int64_t lds, const int32_t* active, int) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_rhs_t: 1 <= k <= 64 columns");
+  g_last_rhs_t_kernel = "host";
+  parallel_for(L.n, nthreads_, [&](int64_t c) {
+    for (int64_t j = 0; j < k; ++j) {
+      double sum = 0.0;
+      if (!active || active[j] != 0) {
+        if (dt == DType::F64) {
+          for (int64_t r = 0; r < L.rows; ++r) {
+            const int64_t g = L.global_row(r);
+            if (g < L.n) sum += tp<double>(P)[r * ldp + c] * V[g * ldv + j];
+          }
+        } else {  // V rounded to fp32, fp32 accumulation, the product widened
+          float acc = 0.0f;
+          for (int64_t r = 0; r < L.rows; ++r) {
+            const int64_t g = L.global_row(r);
+            if (g < L.n) acc += tp<float>(P)[r * ldp + c] * (float)V[g * ldv + j];
+          }
+          sum = (double)acc;
+        }
+      }
+      S[c * lds + j] = sum;
+    }
+  });
+}
+
+void HostDevice::axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S,
+                                  int64_t lds, double sign, int64_t rows, int64_t k, const int32_t* active,
+                                  double* colmax, int) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "axpy_cols_masked: 1 <= k <= 64 columns");
+  for (int64_t j = 0; j < k; ++j) {
+    if (active && active[j] == 0) continue;
+    double mx = 0.0;
+    for (int64_t r = 0; r < rows; ++r) {
+      const double y = (C_in ? C_in[r * ldc + j] : 0.0) + sign * S[r * lds + j];
+      Y[r * ldy + j] = y;
+      mx = max_keep_nan(mx, std::fabs(y));
+    }
+    if (colmax) colmax[j] = mx;
+  }
+}
+
+void HostDevice::col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int) {
+  parallel_for(L.n, nthreads_, [&](int64_t c) {
+    double sum = 0.0;
+    for (int64_t r = 0; r < L.rows; ++r) {
+      if (L.global_row(r) >= L.n) continue;
+      sum += std::fabs(dt == DType::F64 ? tp<double>(X)[r * ldx + c] : (double)tp<float>(X)[r * ldx + c]);
+    }
+    out[c] = sum;
+  });
+}
+
 }  // namespace gj

@@ -770,4 +770,44 @@ void RaceCheckDevice::copy_cols_masked(double* dst, int64_t ldd, const double* s
   inner_->copy_cols_masked(dst, ldd, src, lds, rows, k, mask, s);
 }
 
+void RaceCheckDevice::panel_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V,
+                                  int64_t ldv, int64_t k, double* S, int64_t lds, const int32_t* active, int s) {
+  std::vector<Acc> a;
+  if (k >= 1 && k <= kMaxRhs) {  // (the inner device refuses any other k before it touches memory)
+    int64_t real = 0;  // the real local rows are a prefix: only the last global block row is short
+    for (int64_t b = 0; b < L.nblk; ++b)
+      real += std::max<int64_t>(0, std::min<int64_t>(L.m, L.n - L.global_block(b) * L.m));
+    a.push_back(R(rect(P, ldp, L.n, real, (int64_t)dtype_size(dt)), "P"));
+    for (int64_t b = 0; b < L.nblk; ++b) {  // V: the row blocks this rank owns
+      const int64_t g0 = L.global_block(b) * L.m, h = std::min<int64_t>(L.m, L.n - g0);
+      if (h > 0) a.push_back(R(rect(V + g0 * ldv, ldv, k, h, 8), "V"));
+    }
+    if (active) a.push_back(R(span(active, 4 * k), "active"));
+    a.push_back(W(rect(S, lds, k, L.n, 8), "S"));
+  }
+  check(s, "panel_rhs_t", a);
+  inner_->panel_rhs_t(dt, P, ldp, L, V, ldv, k, S, lds, active, s);
+}
+void RaceCheckDevice::axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S,
+                                       int64_t lds, double sign, int64_t rows, int64_t k, const int32_t* active,
+                                       double* colmax, int s) {
+  std::vector<Acc> a;
+  if (k >= 1 && k <= kMaxRhs) {
+    if (C_in) a.push_back(R(rect(C_in, ldc, k, rows, 8), "C_in"));
+    a.push_back(R(rect(S, lds, k, rows, 8), "S"));
+    if (active) a.push_back(R(span(active, 4 * k), "active"));
+    a.push_back(W(rect(Y, ldy, k, rows, 8), "Y"));
+    if (colmax) a.push_back(W(span(colmax, 8 * k), "colmax"));
+  }
+  check(s, "axpy_cols_masked", a);
+  inner_->axpy_cols_masked(Y, ldy, C_in, ldc, S, lds, sign, rows, k, active, colmax, s);
+}
+void RaceCheckDevice::col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) {
+  int64_t real = 0;
+  for (int64_t b = 0; b < L.nblk; ++b)
+    real += std::max<int64_t>(0, std::min<int64_t>(L.m, L.n - L.global_block(b) * L.m));
+  check(s, "col_abs_sum", {R(rect(X, ldx, L.n, real, (int64_t)dtype_size(dt)), "X"), W(span(out, 8 * L.n), "out")});
+  inner_->col_abs_sum(dt, X, ldx, L, out, s);
+}
+
 }  // namespace gj

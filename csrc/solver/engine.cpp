@@ -2139,13 +2139,19 @@ RhsResult Engine::solve_rhs_impl(const double* b, double* x, const GenSpec* gen,
 // ---------------------------------------------------------------- A X = B, a block of columns
 RhsBlockResult Engine::solve_rhs_block(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                        const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
-                                       int64_t ld, int max_refine, double tol) {
+                                       int64_t ld, int max_refine, double tol, bool trans) {
+  if (trans)
+    return solve_rhs_block_trans_impl(B, ldb, X, ldx, k, false, gen, host_rows, dev_rows_f64, ld, max_refine, tol);
   return solve_rhs_block_impl(B, ldb, X, ldx, k, false, gen, host_rows, dev_rows_f64, ld, max_refine, tol);
 }
 
 RhsBlockResult Engine::solve_rhs_block_device(const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx,
                                               int64_t k, const GenSpec* gen, const double* host_rows,
-                                              const void* dev_rows_f64, int64_t ld, int max_refine, double tol) {
+                                              const void* dev_rows_f64, int64_t ld, int max_refine, double tol,
+                                              bool trans) {
+  if (trans)
+    return solve_rhs_block_trans_impl(B_dev, ldb, X_dev, ldx, k, true, gen, host_rows, dev_rows_f64, ld, max_refine,
+                                      tol);
   return solve_rhs_block_impl(B_dev, ldb, X_dev, ldx, k, true, gen, host_rows, dev_rows_f64, ld, max_refine, tol);
 }
 
@@ -2334,6 +2340,153 @@ RhsBlockResult Engine::solve_rhs_block_impl(const double* B, int64_t ldb, double
     // every column's returned iterate is in `best`
     gather_natural(Vx, best);
     dev_.copy2d(X + c0, ldx * 8, Vx, kw * 8, kg * 8, n, S_MAIN);
+    comm_.drain(dev_, S_MAIN);
+  }
+  out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return out;
+}
+
+// A^T X = B: every product is P_loc^T V_loc summed over the ranks, so B, X and R live in natural row
+// order on every rank, identical bit for bit, and so are the column norms each rank computes.
+RhsBlockResult Engine::solve_rhs_block_trans_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
+                                                  bool on_device, const GenSpec* gen, const double* host_rows,
+                                                  const void* dev_rows, int64_t ld, int max_refine, double tol) {
+  GJ_REQUIRE(solved_, "solve_rhs_block: solve() first");
+  GJ_REQUIRE(k >= 1 && ldb >= k && ldx >= k, "solve_rhs_block: k >= 1 columns, ldb >= k and ldx >= k");
+  GJ_REQUIRE(gen || host_rows || dev_rows || real_local_rows() == 0,
+             "solve_rhs_block: the matrix (generator or rows) is needed for the fp64 residual");
+  const auto t0 = std::chrono::steady_clock::now();
+  const int64_t n = L_.n;
+  const int64_t kw = std::min<int64_t>(k, Device::kMaxRhs);  // widest group = every buffer's leading dimension
+  RhsBlockResult out;
+  out.col.resize((size_t)k);
+  BufSet bufs(dev_);
+  // A's local rows in fp64, once per call
+  double* Aw = bufs.get<double>((size_t)std::max<int64_t>(L_.rows, 1) * L_.npad, false);
+  if (gen) {
+    dev_.generate(DType::F64, Aw, L_, *gen, S_MAIN);
+  } else if (dev_rows) {  // zero + identity padding, then the real rows device-to-device
+    GenSpec z;
+    z.kind = GenKind::Zero;
+    dev_.generate(DType::F64, Aw, L_, z, S_MAIN);
+    const int64_t real = real_local_rows();
+    if (real > 0) dev_.copy2d(Aw, L_.npad * 8, dev_rows, ld * 8, n * 8, real, S_MAIN);
+  } else {
+    upload_rows_into(Aw, DType::F64, host_rows, ld);
+  }
+  // ||A^T||_inf = ||A||_1: the column sums of every rank's rows, summed over the ranks
+  double* csum = bufs.get<double>((size_t)std::max<int64_t>(n, 1));
+  dev_.col_abs_sum(DType::F64, Aw, L_.npad, L_, csum, S_MAIN);
+  comm_.allreduce_sum(dev_, csum, (size_t)n, DType::F64, S_MAIN);
+  std::vector<double> hsum((size_t)n);
+  dev_.copy(hsum.data(), csum, sizeof(double) * (size_t)n, S_MAIN);
+  comm_.drain(dev_, S_MAIN);
+  double an = 0.0;
+  for (double v : hsum) an = max_keep_nan(an, v);
+
+  const size_t nat = (size_t)std::max<int64_t>(n, 1) * kw;
+  double* Vb = bufs.get<double>(nat);     // B
+  double* Vx = bufs.get<double>(nat);     // the iterate X
+  double* Vr = bufs.get<double>(nat);     // the residual R
+  double* Sp = bufs.get<double>(nat);     // a product: this rank's term, then the sum over the ranks
+  double* best = bufs.get<double>(nat);   // the best iterate
+  double* dnorm = bufs.get<double>(2 * Device::kMaxRhs);    // ||r_j|| | ||x_j||
+  int32_t* dflag = bufs.get<int32_t>(2 * Device::kMaxRhs);  // active | save-mask
+  double* hnorm = bufs.get_pinned<double>(2 * Device::kMaxRhs);
+  int32_t* hflag = bufs.get_pinned<int32_t>(2 * Device::kMaxRhs);
+  std::vector<double> hb;  // a device-resident B's columns on the host, for ||b_j|| only
+
+  // dst = C_in + sign * P^T V over all ranks, for the active columns
+  auto product = [&](DType dt, const void* P, const double* V, int64_t kg, const double* C_in, double* dst,
+                     double sign, const int32_t* act, double* colmax) {
+    dev_.panel_rhs_t(dt, P, L_.npad, L_, V, kw, kg, Sp, kw, act, S_MAIN);
+    comm_.allreduce_sum(dev_, Sp, nat, DType::F64, S_MAIN);
+    dev_.axpy_cols_masked(dst, kw, C_in, kw, Sp, kw, sign, n, kg, act, colmax, S_MAIN);
+  };
+
+  for (int64_t c0 = 0; c0 < k; c0 += kw) {
+    const int64_t kg = std::min<int64_t>(kw, k - c0);
+    if (kg < kw) dev_.memset0(Sp, sizeof(double) * nat, S_MAIN);  // the columns past kg enter the sum as 0
+    dev_.copy2d(Vb, kw * 8, B + c0, ldb * 8, kg * 8, n, S_MAIN);
+    std::vector<double> bn((size_t)kg, 0.0);
+    const double* bh = B + c0;
+    int64_t ldh = ldb;
+    if (on_device) {
+      hb.resize((size_t)n * kw);
+      dev_.copy(hb.data(), Vb, sizeof(double) * (size_t)n * kw, S_MAIN);
+      dev_.sync_stream(S_MAIN);
+      bh = hb.data();
+      ldh = kw;
+    }
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t j = 0; j < kg; ++j) bn[(size_t)j] = std::max(bn[(size_t)j], std::fabs(bh[i * ldh + j]));
+    for (double& v : bn)
+      if (v == 0) v = 1;
+
+    // x_0 = inv(A)^T b in the engine dtype, every column active
+    dev_.host_access(hflag, sizeof(int32_t) * 2 * Device::kMaxRhs, true);
+    for (int64_t j = 0; j < Device::kMaxRhs; ++j) hflag[j] = j < kg ? 1 : 0;
+    dev_.copy(dflag, hflag, sizeof(int32_t) * Device::kMaxRhs, S_MAIN);
+    product(opt_.dtype, out_, Vb, kg, nullptr, Vx, 1.0, nullptr, dnorm + Device::kMaxRhs);
+
+    std::vector<int> active((size_t)kg, 1);
+    std::vector<double> best_rn((size_t)kg, 1e300), prev((size_t)kg, 1e300);
+    std::vector<RhsResult> bestr((size_t)kg);
+    RhsResult* rr = out.col.data() + c0;
+    for (int it = 0;; ++it) {
+      // r = b - A^T x in fp64
+      product(DType::F64, Aw, Vx, kg, Vb, Vr, -1.0, dflag, dnorm);
+      dev_.copy(hnorm, dnorm, sizeof(double) * 2 * Device::kMaxRhs, S_MAIN);
+      comm_.drain(dev_, S_MAIN);
+      dev_.host_access(hnorm, sizeof(double) * 2 * Device::kMaxRhs, false);
+      out.sweeps = std::max(out.sweeps, it + 1);
+      // the per-column decision of solve_rhs
+      dev_.host_access(hflag, sizeof(int32_t) * 2 * Device::kMaxRhs, true);
+      bool any = false;
+      for (int64_t j = 0; j < kg; ++j) {
+        int32_t save = 0;
+        if (active[(size_t)j]) {
+          const double rn = hnorm[j], xn = hnorm[Device::kMaxRhs + j];
+          RhsResult& r = rr[j];
+          r.history.push_back(rn / bn[(size_t)j]);
+          r.residual = rn;
+          r.backward_error = rn / (an * xn + bn[(size_t)j]);
+          if (r.backward_error <= tol) {
+            r.converged = true;
+            active[(size_t)j] = 0;
+            save = 1;
+          } else {
+            if (rn < best_rn[(size_t)j]) {
+              best_rn[(size_t)j] = rn;
+              bestr[(size_t)j] = r;
+              save = 1;
+            }
+            if (it >= max_refine || (it > 0 && rn > 0.5 * prev[(size_t)j])) {  // budget spent / not contracting
+              if (rn > best_rn[(size_t)j]) {  // the best iterate (already saved), with its own residual
+                bestr[(size_t)j].history = r.history;
+                r = bestr[(size_t)j];
+              } else {
+                save = 1;
+              }
+              active[(size_t)j] = 0;
+            } else {
+              prev[(size_t)j] = rn;
+              r.steps = it + 1;
+            }
+          }
+        }
+        hflag[j] = active[(size_t)j];
+        hflag[Device::kMaxRhs + j] = save;
+        any = any || active[(size_t)j];
+      }
+      dev_.copy(dflag, hflag, sizeof(int32_t) * 2 * Device::kMaxRhs, S_MAIN);
+      dev_.copy_cols_masked(best, kw, Vx, kw, n, kg, dflag + Device::kMaxRhs, S_MAIN);
+      if (!any) break;
+      // x += inv(A)^T r for the columns still active (engine dtype, added in fp64)
+      product(opt_.dtype, out_, Vr, kg, Vx, Vx, 1.0, dflag, dnorm + Device::kMaxRhs);
+    }
+    // every column's returned iterate is in `best`
+    dev_.copy2d(X + c0, ldx * 8, best, kw * 8, kg * 8, n, S_MAIN);
     comm_.drain(dev_, S_MAIN);
   }
   out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

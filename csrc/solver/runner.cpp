@@ -165,7 +165,7 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
       res = eng->residual_generated(cfg.gen);
     }
   }
-  if (!sh.b.empty() && cfg.nrhs > 1) {
+  if (!sh.b.empty() && (cfg.nrhs > 1 || cfg.trans)) {  // trans: the block path at any width
     const int64_t k = cfg.nrhs;
     std::vector<double> x((size_t)cfg.n * k);
     comm->barrier(*dev);
@@ -174,7 +174,7 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
     if (src && local.empty()) load();  // the fp64 rows of A (residual_rows keeps them in `local`)
     const RhsBlockResult br = eng->solve_rhs_block(sh.b.data(), k, x.data(), k, k, src ? nullptr : &cfg.gen,
                                                    src ? local.data() : nullptr, nullptr, cfg.n, refine,
-                                                   cfg.refine_tol);
+                                                   cfg.refine_tol, cfg.trans);
     const double tx = comm->host_max(
         *dev, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     if (rank == 0) {
@@ -182,6 +182,7 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
       RunReport& r = sh.rep;
       r.rhs_solved = true;
       r.nrhs = (int)k;
+      r.trans = cfg.trans;
       r.rhs_cols = br.col;
       r.rhs_converged = true;
       size_t worst = 0;

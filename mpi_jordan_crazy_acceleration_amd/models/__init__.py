@@ -1,2 +1,2 @@
 """Solver "models": the block Gauss-Jordan inverter and the linear-system solver built on it."""
-from .gauss_jordan import GaussJordan, inverse, run, solve  # noqa: F401
+from .gauss_jordan import Factored, GaussJordan, factor, inverse, run, solve  # noqa: F401

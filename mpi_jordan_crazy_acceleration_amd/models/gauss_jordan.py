@@ -67,11 +67,14 @@ class GaussJordan:
 
     def run(self, n: int, gen: str = "absdiff", seed: int = 0, file: Optional[str] = None,
             input: Optional[np.ndarray] = None, keep_inverse: bool = False, repeats: int = 1,
-            rhs=None, keep_solution: bool = False, profile: bool = False, nrhs: int = 1) -> dict:
+            rhs=None, keep_solution: bool = False, profile: bool = False, nrhs: int = 1,
+            trans: bool = False) -> dict:
         """One CLI-equivalent run.  ``rhs``: None, "ones", "random", a file path, an n-vector or an
         n x k matrix — then x = inv(A) b is computed on the devices, refined in fp64, and
         ``axb_residual`` = ||A x - b||_inf reported.  ``nrhs`` > 1 (implied by a matrix): the block
-        path, all columns per sweep (``axb_columns``: one info per column, ``x``: n x nrhs)."""
+        path, all columns per sweep (``axb_columns``: one info per column, ``x``: n x nrhs).
+        ``trans``: A^T x = b from the same inverse (the block path at any width); ``axb_residual`` is
+        then ||A^T x - b||_inf and the report holds ``trans`` = True."""
         cfg = self._cfg(n)
         cfg.update(gen=gen, seed=int(seed), keep_inverse=keep_inverse, repeats=int(repeats),
                    keep_solution=bool(keep_solution), profile=bool(profile))
@@ -87,6 +90,8 @@ class GaussJordan:
                 nrhs = r.shape[1]
             cfg["rhs_input"] = np.ascontiguousarray(r.reshape(-1))
         cfg["nrhs"] = int(nrhs)
+        if trans:
+            cfg["trans"] = True
         rep = load_native().run_local(cfg)
         rep["status_name"] = STATUS.get(rep["status"], "error")
         return rep
@@ -138,32 +143,115 @@ class GaussJordan:
         eng.download_rows_device(out.data_ptr(), out.stride(0))
         return out.to(A.dtype)
 
-    def solve_resident(self, A: torch.Tensor, b, max_refine: int = -1, tol: float = 1e-15):
+    def factor(self, A) -> "Factored":
+        """Invert A once and keep the engine: see :func:`factor`."""
+        return Factored(self, A)
+
+    def solve_resident(self, A: torch.Tensor, b, max_refine: int = -1, tol: float = 1e-15, trans: bool = False):
         """A x = b for a CUDA tensor A through the engine (Engine::solve_rhs_device): x = inv(A) b by
         the native GEMV, then iterative refinement with the residual b - A x in fp64 against A's
         rows (an fp32 inverse refines to fp64 accuracy on a well-conditioned system, as the CLI's
         --rhs path).  b: an n-vector, or an n x k matrix: then Engine::solve_rhs_block refines all
         columns together on the device (one pass over each matrix per sweep, B and X never leave the
-        GPU).  Returns (x on A's device in A's dtype with b's shape, info per column)."""
+        GPU).  ``trans``: A^T x = b from the same inverse, always by the block path (a vector is one
+        column).  Returns (x on A's device in A's dtype with b's shape, info per column)."""
         eng, _ = self._engine_resident(A)
         a64 = A.detach().to(torch.float64).contiguous()
-        if np.ndim(b) != 2 or np.shape(b)[1] == 1:  # one right-hand side: the one-vector path
-            torch.cuda.synchronize(a64.device)
-            bt = b.detach().to("cpu", torch.float64) if isinstance(b, torch.Tensor) else \
-                torch.as_tensor(np.asarray(b, dtype=np.float64))
-            x, info = eng.solve_rhs_device(np.ascontiguousarray(bt.reshape(-1).numpy()), a64.data_ptr(),
-                                           a64.stride(0), int(max_refine), float(tol))
-            return torch.from_numpy(x.reshape(bt.shape)).to(device=A.device, dtype=A.dtype), [info]
-        b64 = (b.detach() if isinstance(b, torch.Tensor) else torch.as_tensor(np.asarray(b, dtype=np.float64)))
-        b64 = b64.to(device=a64.device, dtype=torch.float64).contiguous()
-        if b64.shape[0] != a64.shape[0] or b64.shape[1] < 1:
-            raise ValueError("b must have n rows and at least one column")
-        x64 = torch.empty_like(b64)
+        return _solve_on_device(eng, a64, A.dtype, b, max_refine, tol, trans)
+
+
+def _solve_on_device(eng, a64: torch.Tensor, out_dtype, b, max_refine: int, tol: float, trans: bool):
+    """solve_resident's solve against an engine that holds inv(A); a64 = A's rows in fp64 on the GPU,
+    x is returned there in out_dtype"""
+    if trans and np.ndim(b) == 1:
+        bt = b.detach() if isinstance(b, torch.Tensor) else torch.as_tensor(np.asarray(b, dtype=np.float64))
+        x, infos = _solve_on_device(eng, a64, out_dtype, bt.reshape(-1, 1), max_refine, tol, True)
+        return x.reshape(-1), infos
+    if not trans and (np.ndim(b) != 2 or np.shape(b)[1] == 1):  # one right-hand side: the one-vector path
         torch.cuda.synchronize(a64.device)
-        _, infos, _ = eng.solve_rhs_block(rows_f64=a64.data_ptr(), ld=a64.stride(0), b_dev=b64.data_ptr(),
-                                          ldb=b64.stride(0), x_dev=x64.data_ptr(), ldx=x64.stride(0),
-                                          ncols=b64.shape[1], max_refine=int(max_refine), tol=float(tol))
-        return x64.to(A.dtype), list(infos)
+        bt = b.detach().to("cpu", torch.float64) if isinstance(b, torch.Tensor) else \
+            torch.as_tensor(np.asarray(b, dtype=np.float64))
+        x, info = eng.solve_rhs_device(np.ascontiguousarray(bt.reshape(-1).numpy()), a64.data_ptr(),
+                                       a64.stride(0), int(max_refine), float(tol))
+        return torch.from_numpy(x.reshape(bt.shape)).to(device=a64.device, dtype=out_dtype), [info]
+    b64 = (b.detach() if isinstance(b, torch.Tensor) else torch.as_tensor(np.asarray(b, dtype=np.float64)))
+    b64 = b64.to(device=a64.device, dtype=torch.float64).contiguous()
+    if b64.shape[0] != a64.shape[0] or b64.shape[1] < 1:
+        raise ValueError("b must have n rows and at least one column")
+    x64 = torch.empty_like(b64)
+    torch.cuda.synchronize(a64.device)
+    _, infos, _ = eng.solve_rhs_block(rows_f64=a64.data_ptr(), ld=a64.stride(0), b_dev=b64.data_ptr(),
+                                      ldb=b64.stride(0), x_dev=x64.data_ptr(), ldx=x64.stride(0),
+                                      ncols=b64.shape[1], max_refine=int(max_refine), tol=float(tol),
+                                      trans=bool(trans))
+    return x64.to(out_dtype), list(infos)
+
+
+class Factored:
+    """inv(A), computed once and kept for any number of solves (:func:`factor`).
+
+    ``solve(b, trans=False)``: A x = b, or A^T x = b with ``trans`` -- from the same inverse, no
+    second inversion -- for an n-vector or an n x k matrix b, refined in fp64 against A's rows (which
+    the object keeps in fp64); returns b's shape and type.  ``inverse()``: the inverse in A's type.
+    ``n``, ``dtype`` ("fp64" | "fp32": the engine's arithmetic); ``infos``: the per-column refinement
+    results of the last solve.  A CUDA tensor A stays on its GPU (the resident engine); a numpy
+    array or a CPU tensor runs one host rank."""
+
+    def __init__(self, gj: "GaussJordan", A):
+        self._is_torch = isinstance(A, torch.Tensor)
+        self._like = A if self._is_torch else None
+        self.dtype = gj.dtype
+        self.infos: list = []
+        if self._is_torch and A.is_cuda:
+            self._cuda = True
+            self._eng, self._a = gj._engine_resident(A)
+            self._a64 = A.detach().to(torch.float64).contiguous()
+            self.n = int(A.shape[0])
+            return
+        self._cuda = False
+        a = A.detach().to("cpu", torch.float64).numpy() if self._is_torch else np.asarray(A, dtype=np.float64)
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("A must be square")
+        C = load_native()
+        self.n = int(a.shape[0])
+        self._a64 = np.ascontiguousarray(a)
+        self._eng = C.Engine(C.host_device(int(gj.host_threads)), C.self_comm(), self.n, int(gj.block_size),
+                             gj.dtype, int(gj.chunk_cols), float(gj.eps), bool(gj.sync_debug), int(gj.depth),
+                             pivot=gj.pivot)
+        self._eng.upload_local_rows(self._a64)
+        st = self._eng.solve()
+        if st["status"] == 1:
+            raise SingularMatrixError("singular matrix")
+        if st["status"] != 0:
+            raise RuntimeError(STATUS.get(st["status"], "error"))
+
+    def solve(self, b, trans: bool = False, max_refine: int = -1, tol: float = 1e-15):
+        if self._cuda:
+            out_dtype = b.dtype if isinstance(b, torch.Tensor) else self._like.dtype
+            x, self.infos = _solve_on_device(self._eng, self._a64, out_dtype, b, max_refine, tol, trans)
+            return x
+        b_torch = isinstance(b, torch.Tensor)
+        bn = b.detach().to("cpu", torch.float64).numpy() if b_torch else np.asarray(b, dtype=np.float64)
+        if bn.ndim not in (1, 2) or bn.shape[0] != self.n:
+            raise ValueError("b must be an n-vector or an n x k matrix")
+        if not trans and (bn.ndim == 1 or bn.shape[1] == 1):  # the one-vector path, as gj.solve
+            x, info = self._eng.solve_rhs_rows(np.ascontiguousarray(bn.reshape(-1)), self._a64, int(max_refine),
+                                               float(tol))
+            self.infos = [info]
+        else:
+            x, infos, _ = self._eng.solve_rhs_block(np.ascontiguousarray(bn.reshape(self.n, -1)), rows=self._a64,
+                                                    max_refine=int(max_refine), tol=float(tol), trans=bool(trans))
+            self.infos = list(infos)
+        x = x.reshape(bn.shape)
+        return torch.from_numpy(x).to(device=b.device, dtype=b.dtype) if b_torch else x
+
+    def inverse(self):
+        if self._cuda:
+            out = torch.empty_like(self._a)
+            self._eng.download_rows_device(out.data_ptr(), out.stride(0))
+            return out.to(self._like.dtype)
+        inv = self._eng.download_local_rows()
+        return torch.from_numpy(inv).to(device=self._like.device, dtype=self._like.dtype) if self._is_torch else inv
 
 
 _HIP_DEVICES: dict = {}
@@ -180,8 +268,16 @@ def inverse(A, block_size: int = 128, **kw):
     return GaussJordan(block_size=block_size, residual="never", **kw).inverse(A)
 
 
-def solve(A, b, block_size: int = 128, **kw):
-    """Solve ``A x = b`` via the block Gauss-Jordan inverse.
+def factor(A, block_size: int = 128, **kw) -> Factored:
+    """Invert A once and return a :class:`Factored` handle: ``F.solve(b)``, ``F.solve(c, trans=True)``
+    and ``F.inverse()`` all come from that one inversion (a forward plus an adjoint solve costs one
+    inversion, not two)."""
+    return GaussJordan(block_size=block_size, residual="never", **kw).factor(A)
+
+
+def solve(A, b, block_size: int = 128, trans: bool = False, **kw):
+    """Solve ``A x = b`` (``trans``: ``A^T x = b``, from the inverse of A itself) via the block
+    Gauss-Jordan inverse.
 
     Every right-hand side runs the native path, x = inv(A) b on the devices next to the inverse's
     rows, refined in fp64 (never a bare ``inv @ b``): a vector through Engine::solve_rhs, a matrix
@@ -191,13 +287,13 @@ def solve(A, b, block_size: int = 128, **kw):
     is_torch = isinstance(A, torch.Tensor)
     if is_torch and A.is_cuda:
         gj = GaussJordan(block_size=block_size, residual="never", **kw)
-        x, _ = gj.solve_resident(A, b)
+        x, _ = gj.solve_resident(A, b, trans=trans)
         return x
     bn = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, dtype=np.float64)
     if bn.ndim in (1, 2):
         a = A.detach().to("cpu", torch.float64).numpy() if is_torch else np.asarray(A, dtype=np.float64)
         gj = GaussJordan(block_size=block_size, residual="never", **kw)
-        rep = gj.run(a.shape[0], input=a, rhs=bn, keep_solution=True)
+        rep = gj.run(a.shape[0], input=a, rhs=bn, keep_solution=True, trans=trans)
         if rep["status"] == 1:
             raise SingularMatrixError("singular matrix")
         if rep["status"] != 0:

@@ -242,3 +242,50 @@ def copy_cols_masked(dst: torch.Tensor, src: torch.Tensor, mask: torch.Tensor) -
     device_for(dst).copy_cols_masked(_p(dst), dst.stride(0), _p(src), src.stride(0), dst.shape[0], dst.shape[1],
                                      _p(mask))
     return dst
+
+
+def panel_rhs_t(P: torch.Tensor, V: torch.Tensor, S: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0,
+                active: torch.Tensor = None, ncols: int = None) -> torch.Tensor:
+    """S[c, j] = sum over this rank's real local rows r of P[r, c] * V[grow(r), j] for c < n
+    (Device::panel_rhs_t): rank ``k``'s term of P_full^T V.  ``P`` this rank's rows of a panel (fp64 /
+    fp32, rows x >= n), ``V`` the whole block in natural row order (fp64, >= n rows; only the rows
+    this rank owns are read), ``S`` fp64 with >= n rows, ``active`` int32[ncols] or None (a column
+    with 0 is not computed and gets +0.0).  Views with unit column stride; ``ncols`` defaults to S's
+    width (1..64, else an error)."""
+    assert V.dtype == S.dtype == torch.float64 and P.stride(-1) == 1 and V.stride(-1) == 1 and S.stride(-1) == 1
+    ncols = S.shape[1] if ncols is None else int(ncols)
+    if active is not None:
+        assert active.dtype == torch.int32 and active.is_contiguous()
+    device_for(S).panel_rhs_t(_DT[P.dtype], _p(P), P.stride(0), n, m, p, k, _p(V), V.stride(0), ncols, _p(S),
+                              S.stride(0), 0 if active is None else _p(active))
+    return S
+
+
+def axpy_cols_masked(Y: torch.Tensor, S: torch.Tensor, C_in: torch.Tensor = None, sign: float = 1.0,
+                     active: torch.Tensor = None, colmax: torch.Tensor = None, ncols: int = None) -> torch.Tensor:
+    """Y[:, j] = C_in[:, j] + sign * S[:, j] for the columns with active[j] != 0 (Device::axpy_cols_masked;
+    fp64 views, ``C_in`` None = 0 or Y itself, ``active`` int32 or None = all), ``colmax[j]`` = max |Y[:, j]|
+    with NaN kept; an inactive column's Y and colmax stay untouched.  ``ncols`` defaults to Y's width
+    (1..64, else an error)."""
+    assert Y.dtype == S.dtype == torch.float64 and Y.stride(-1) == 1 and S.stride(-1) == 1
+    ncols = Y.shape[1] if ncols is None else int(ncols)
+    cp, ldc = 0, 0
+    if C_in is not None:
+        assert C_in.dtype == torch.float64 and C_in.stride(-1) == 1
+        cp, ldc = _p(C_in), C_in.stride(0)
+    if active is not None:
+        assert active.dtype == torch.int32 and active.is_contiguous()
+    if colmax is not None:
+        assert colmax.dtype == torch.float64 and colmax.is_contiguous()
+    device_for(Y).axpy_cols_masked(_p(Y), Y.stride(0), cp, ldc, _p(S), S.stride(0), float(sign), Y.shape[0], ncols,
+                                   0 if active is None else _p(active), 0 if colmax is None else _p(colmax))
+    return Y
+
+
+def col_abs_sum(X: torch.Tensor, out: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0) -> torch.Tensor:
+    """out[c] = sum over this rank's real local rows of |X[r, c]| for c < n (Device::col_abs_sum):
+    rank ``k``'s term of the column sums, accumulated in fp64 with NaN kept.  ``X`` fp64 / fp32 with
+    unit column stride, ``out`` fp64, contiguous, >= n entries."""
+    assert out.dtype == torch.float64 and out.is_contiguous() and X.stride(-1) == 1
+    device_for(out).col_abs_sum(_DT[X.dtype], _p(X), X.stride(0), n, m, p, k, _p(out))
+    return out

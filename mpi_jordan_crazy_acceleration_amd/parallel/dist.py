@@ -206,12 +206,14 @@ class DistributedGaussJordan:
         return self.engine.solve()
 
     def solve_rhs(self, B: np.ndarray, A_rows: Optional[np.ndarray] = None, gen=None, max_refine: int = -1,
-                  tol: float = 1e-15):
+                  tol: float = 1e-15, trans: bool = False):
         """Collective, after solve(): A X = B for the n x k block B (an n-vector counts as k = 1),
         the same full B on every rank, every column refined in fp64 (Engine::solve_rhs_block).  The
         fp64 matrix comes from ``gen`` = (kind, seed) or from ``A_rows``, this rank's rows of A (in
-        global_row_ids() order) or the full n x n matrix.  Returns (X with B's shape, one info dict
-        per column), the same on every rank."""
+        global_row_ids() order) or the full n x n matrix.  ``trans``: A^T X = B from the same inverse
+        (each rank's term of inv(A)^T B over its own rows, summed over the ranks: no transpose of the
+        distributed matrix).  Returns (X with B's shape, one info dict per column), the same on every
+        rank."""
         B = np.asarray(B, dtype=np.float64)
         b2 = np.ascontiguousarray(B.reshape(self.n, -1))
         rows = None
@@ -225,7 +227,7 @@ class DistributedGaussJordan:
         else:
             gen = (str(gen[0]), int(gen[1]))
         x, infos, _ = self.engine.solve_rhs_block(b2, gen=gen, rows=rows, max_refine=int(max_refine),
-                                                  tol=float(tol))
+                                                  tol=float(tol), trans=bool(trans))
         return x.reshape(B.shape), list(infos)
 
     # ---- output
