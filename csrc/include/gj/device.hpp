@@ -452,6 +452,27 @@ class Device {
   // rank's term of the column sums (||A||_1 after a sum over the ranks).  X is L.rows x L.npad of
   // dtype dt, leading dimension ldx; accumulated in fp64, NaN kept; padding never read.
   virtual void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) = 0;
+
+  // ---- the low-rank update of a resident panel (Engine::update_inverse) ----
+  // X[r][c] = round_dt(X[r][c] + sign * sum_{j<k} W[wrow(r)][j] * Z[c][j]) for this rank's local rows r
+  // whose global row grow(r) = ((r / m) * p + rank) * m + r % m is below L.n, and the columns c < L.n;
+  // 1 <= k <= kMaxRhs (else Status::BadArgs).
+  //   X     this rank's rows of a panel, L.rows x L.npad of dtype dt, leading dimension ldx, in place
+  //   W     fp64, k columns, leading dimension ldw.  w_natural = false: local row order, wrow(r) = r
+  //         (what panel_rhs writes); w_natural = true: n x k in natural order, wrow(r) = grow(r) (a
+  //         kept copy of A's rows takes A_loc += U_loc V^T without a gather)
+  //   Z     fp64, n x k in natural row order, leading dimension ldz
+  //   sign  +1 or -1
+  // Both dtypes: the k products and their sum in fp64, the panel element widened, the sum added, the
+  // result rounded once to dt.  Never read or written: X's rows with global row >= n, X's columns
+  // >= n and every pitch gap, so the padding identity of diag(A, I) survives bit for bit.  Never
+  // read: W's rows of padded local rows (and, w_natural, of other ranks), Z's rows >= n.  A NaN or an
+  // Inf of W or Z reaches every element it is a term of, also through a zero factor (the rule of
+  // gemm).  No atomics and no split of the k sum: two launches on the same inputs give the same bits.
+  // GPU: a leading dimension ldx whose rows one tile cannot address with 32-bit byte offsets is
+  // refused with Status::BadArgs.
+  virtual void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw,
+                           bool w_natural, const double* Z, int64_t ldz, int64_t k, double sign, int s) = 0;
 };
 
 // Test probe of Device::panel_rhs, like g_last_gemm_kernel: "host" on the host executor,
@@ -459,5 +480,7 @@ class Device {
 inline thread_local const char* g_last_rhs_kernel = "";
 // The same of Device::panel_rhs_t: "host", or "rhst<16|32|64>:<f64|f32>:<vec|scalar>:s<split>".
 inline thread_local const char* g_last_rhs_t_kernel = "";
+// The same of Device::rank_update: "host", or "rku<k padded to 4>:<f64|f32>:<vec|scalar>".
+inline thread_local const char* g_last_rank_update_kernel = "";
 
 }  // namespace gj

@@ -132,6 +132,15 @@ struct RhsBlockResult {
   double seconds = 0;
 };
 
+// Result of Engine::update_inverse.
+struct UpdateResult {
+  Status status = Status::Ok;    // Singular: the update was refused and nothing was written
+  int64_t k = 0;                 // rank of the update
+  double min_pivot = 0;          // smallest |pivot| of the LU of C = I + V^T inv(A) U, over max(1, max|C - I|)
+  double cond1 = 0;              // ||C||_1 ||inv(C)||_1 (0 when refused)
+  double seconds = 0;            // this rank's wall time of the call
+};
+
 class Engine {
  public:
   Engine(Device& dev, Comm& comm, int64_t n, int64_t m, const SolveOptions& opt);
@@ -218,6 +227,22 @@ class Engine {
   RhsBlockResult solve_rhs_block_device(const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx, int64_t k,
                                         const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
                                         int64_t ld, int max_refine, double tol, bool trans = false);
+  // Low-rank update of the resident inverse (after solve()): the result panel becomes
+  // inv(A + U V^T) = X - (X U) inv(C) (V^T X), C = I_k + V^T X U, X = inv(A), by one pass over X and
+  // O(n^2 k) flops instead of another inversion.  Collective.  U and V are n x k, row-major (ldu,
+  // ldv >= k), fp64, full on every rank; 1 <= k <= Device::kMaxRhs, a larger k is BadArgs (callers
+  // apply it in pieces).  W_loc = X U (Device::panel_rhs) and Z = X^T V (Device::panel_rhs_t +
+  // Comm::allreduce_sum) in the engine dtype's arithmetic, C on every rank from the same Z and U, its
+  // LU with partial pivoting in fp64 on the host, then Device::rank_update with W_loc inv(C) and Z.
+  // Refused with Status::Singular, before anything is written (the panel stays bitwise as it was),
+  // when a pivot of C is non-finite or |pivot| <= SolveOptions::eps * max(1, max|C - I|): the engine's
+  // scalar-pivot rule applied to C.  A near-singular update that passes is accepted and reported
+  // through min_pivot and cond1.
+  // The engine does not hold A: every solve_rhs* / residual_* call after an update must be given the
+  // rows of A + U V^T, and generator-based calls (gen, residual_generated) no longer describe it.
+  UpdateResult update_inverse(const double* U, int64_t ldu, const double* V, int64_t ldv, int64_t k);
+  // The same with U and V in device memory (fp64), e.g. torch CUDA tensors.
+  UpdateResult update_inverse_device(const double* U_dev, int64_t ldu, const double* V_dev, int64_t ldv, int64_t k);
   // Precision of the last residual: true = fp64 (always for fp64 solves; fp32 solves when it fits).
   bool residual_fp64() const { return last_residual_fp64_; }
   // ||A||_inf of the last solve's input (the reference's norm, taken at solve start) and
@@ -294,6 +319,7 @@ class Engine {
   RhsBlockResult solve_rhs_block_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                       bool on_device, const GenSpec* gen, const double* host_rows,
                                       const void* dev_rows, int64_t ld, int max_refine, double tol);
+  UpdateResult update_inverse_impl(const double* U, int64_t ldu, const double* V, int64_t ldv, int64_t k);
   RhsBlockResult solve_rhs_block_trans_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                             bool on_device, const GenSpec* gen, const double* host_rows,
                                             const void* dev_rows, int64_t ld, int max_refine, double tol);

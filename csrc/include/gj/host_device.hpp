@@ -93,6 +93,8 @@ class HostDevice : public Device {
   void axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S, int64_t lds,
                         double sign, int64_t rows, int64_t k, const int32_t* active, double* colmax, int s) override;
   void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) override;
+  void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw, bool w_natural,
+                   const double* Z, int64_t ldz, int64_t k, double sign, int s) override;
 
  private:
   int nthreads_ = 1;

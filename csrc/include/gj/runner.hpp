@@ -41,6 +41,13 @@ struct RunConfig {
   // A^T x = b from the same inverse (Engine::solve_rhs_block with trans, at any nrhs >= 1); the
   // reported residual is then ||A^T x - b||_inf
   bool trans = false;
+  // A low-rank update after the inversion (Engine::update_inverse): caller-owned n x update_k
+  // row-major U and V, or null.  The inverse becomes that of A + U V^T, and the right-hand-side
+  // solve, the residual and keep_inverse then refer to A + U V^T (every rank forms its fp64 rows of
+  // it on the host, from the input matrix or the generator).
+  const double* update_u = nullptr;
+  const double* update_v = nullptr;
+  int64_t update_k = 0;
   bool keep_solution = false;         // return x in RunReport::x
   // iterative refinement of x with the residual in fp64 (Engine::solve_rhs): at most `refine`
   // steps (-1 = auto: 10 for fp32 solves, 2 for fp64), stop at backward error <= refine_tol
@@ -80,6 +87,8 @@ struct RunReport {
   int nrhs = 1;
   bool trans = false;               // the right-hand sides were solved against A^T
   std::vector<RhsResult> rhs_cols;
+  bool updated = false;             // RunConfig::update_u / update_v were applied
+  UpdateResult update;              // rank 0's result of it
   // race_check: unordered conflicting accesses found (total, the first distinct ones described),
   // ops checked
   int64_t race_count = 0;

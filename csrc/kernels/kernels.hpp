@@ -158,5 +158,11 @@ void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* 
 void set_rhs_t_split(int s);
 const char* last_rhs_t_kernel();
 
+// rank_update.hip: Device::rank_update, one pass over X.  Test probe: the name of this thread's last
+// launch, "rku<k padded to 4>:<f64|f32>:<vec|scalar>" ("host" on the host executor).
+void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw, bool w_natural,
+                 const double* Z, int64_t ldz, int64_t k, double sign, hipStream_t s);
+const char* last_rank_update_kernel();
+
 }  // namespace kern
 }  // namespace gj

@@ -231,6 +231,9 @@ PYBIND11_MODULE(_C, mod) {
   mod.def("last_rhs_t_kernel", [] { return std::string(kern::last_rhs_t_kernel()); },
           "test probe: 'rhst<16|32|64>:<f64|f32>:<vec|scalar>:s<split>' of this thread's last Device.panel_rhs_t "
           "('host' on the host executor)");
+  mod.def("last_rank_update_kernel", [] { return std::string(kern::last_rank_update_kernel()); },
+          "test probe: 'rku<k padded to 4>:<f64|f32>:<vec|scalar>' of this thread's last Device.rank_update "
+          "('host' on the host executor)");
   mod.def("set_lat_glds", [](bool on) { kern::set_lat_glds(on ? 1 : 0); },
           "every latency GEMM of >= 1024 rows on the LDS-DMA kernel (tests; the engine sets it per launch)");
 
@@ -472,6 +475,26 @@ PYBIND11_MODULE(_C, mod) {
              d.sync_stream(S_MAIN);
              return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
            })
+      // The same timing of rank_update (X -= / += W Z^T in turn, so that X stays bounded), W in local order
+      .def("time_rank_update",
+           [lay](Device& d, const std::string& dt, U X, int64_t ldx, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U W, int64_t ldw, U Z, int64_t ldz, int64_t ncols, int reps) {
+             py::gil_scoped_release rel;
+             const Layout L = lay(n, m, p, k);
+             const DType t = parse_dtype(dt);
+             auto run = [&](double sign) {
+               d.rank_update(t, (void*)X, ldx, L, (const double*)W, ldw, false, (const double*)Z, ldz, ncols, sign,
+                             S_MAIN);
+             };
+             run(-1.0);
+             run(1.0);
+             const int e0 = d.create_event(true), e1 = d.create_event(true);
+             d.record(e0, S_MAIN);
+             for (int i = 0; i < reps; ++i) run(i % 2 ? 1.0 : -1.0);
+             d.record(e1, S_MAIN);
+             d.sync_stream(S_MAIN);
+             return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
+           })
       .def("time_gemm_store_kmajor",
            [](Device& d, const std::string& dt, int64_t M, int64_t N, int64_t K, U A, int64_t lda, U B, int64_t ldb,
               U C, int64_t ldc, int reps) {
@@ -608,6 +631,18 @@ PYBIND11_MODULE(_C, mod) {
            },
            py::arg("dt"), py::arg("P"), py::arg("ldp"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"),
            py::arg("V"), py::arg("ldv"), py::arg("ncols"), py::arg("S"), py::arg("lds"), py::arg("active") = U(0))
+      // X += sign * W Z^T over this rank's real rows and the columns < n, rounded once (in place)
+      .def("rank_update",
+           [lay](Device& d, const std::string& dt, U X, int64_t ldx, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U W, int64_t ldw, bool w_natural, U Z, int64_t ldz, int64_t ncols, double sign) {
+             py::gil_scoped_release rel;
+             d.rank_update(parse_dtype(dt), (void*)X, ldx, lay(n, m, p, k), (const double*)W, ldw, w_natural,
+                           (const double*)Z, ldz, ncols, sign, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("dt"), py::arg("X"), py::arg("ldx"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"),
+           py::arg("W"), py::arg("ldw"), py::arg("w_natural"), py::arg("Z"), py::arg("ldz"), py::arg("ncols"),
+           py::arg("sign"))
       .def("axpy_cols_masked",
            [](Device& d, U Y, int64_t ldy, U C_in, int64_t ldc, U S, int64_t lds, double sign, int64_t rows,
               int64_t ncols, U active, U colmax) {
@@ -982,6 +1017,40 @@ PYBIND11_MODULE(_C, mod) {
            "in fp64 against A given as gen=(kind, seed), rows (this rank's fp64 rows, host) or rows_f64 / ld (an "
            "fp64 device array).  B: an (n, k) host array -> returns (X, infos, meta); or b_dev / x_dev device "
            "pointers (fp64, n x ncols) -> X is written in place and returned as None")
+      .def("update_inverse",
+           [](PyEngine& e, py::object Uo, py::object Vo, uintptr_t u_dev, int64_t ldu, uintptr_t v_dev, int64_t ldv,
+              int64_t ncols) {
+             const int64_t n = e.eng->layout().n;
+             UpdateResult ur;
+             if (u_dev || v_dev) {  // U and V in device memory (fp64, n x ncols)
+               if (!u_dev || !v_dev || ncols < 1 || ldu < ncols || ldv < ncols)
+                 throw std::invalid_argument("device U / V: both pointers, ncols >= 1, ldu >= ncols, ldv >= ncols");
+               py::gil_scoped_release rel;
+               ur = e.eng->update_inverse_device(reinterpret_cast<const double*>(u_dev), ldu,
+                                                 reinterpret_cast<const double*>(v_dev), ldv, ncols);
+             } else {
+               auto u = Uo.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+               auto v = Vo.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+               if (u.ndim() != 2 || u.shape(0) != n || u.shape(1) < 1 || v.ndim() != 2 || v.shape(0) != n ||
+                   v.shape(1) != u.shape(1))
+                 throw std::invalid_argument("U and V must be (n, k) arrays, k >= 1");
+               const int64_t k = u.shape(1);
+               py::gil_scoped_release rel;
+               ur = e.eng->update_inverse(u.data(), k, v.data(), k, k);
+             }
+             py::dict info;
+             info["status"] = (int)ur.status;
+             info["k"] = ur.k;
+             info["min_pivot"] = ur.min_pivot;
+             info["cond1"] = ur.cond1;
+             info["seconds"] = ur.seconds;
+             return info;
+           },
+           py::arg("U") = py::none(), py::arg("V") = py::none(), py::arg("u_dev") = 0, py::arg("ldu") = 0,
+           py::arg("v_dev") = 0, py::arg("ldv") = 0, py::arg("ncols") = 0,
+           "inv(A) -> inv(A + U V^T) in the result panel (Engine::update_inverse; collective): U, V (n, k) host "
+           "arrays, or u_dev / v_dev device pointers (fp64, n x ncols).  status 1 = refused as singular, nothing "
+           "written.  Later solve_rhs* / residual_* calls must be given the rows of A + U V^T")
       .def("solve_rhs_rows",
            [](PyEngine& e, py::array_t<double, py::array::c_style | py::array::forcecast> b,
               py::array_t<double, py::array::c_style | py::array::forcecast> rows, int max_refine, double tol) {
@@ -1168,6 +1237,17 @@ PYBIND11_MODULE(_C, mod) {
       if (rhs_in.size() != c.n * c.nrhs) throw std::invalid_argument("rhs_input must have n * nrhs entries");
       c.rhs_input = rhs_in.data();
     }
+    py::array_t<double, py::array::c_style | py::array::forcecast> upd_u, upd_v;
+    if (d.contains("update_u") && !d["update_u"].is_none()) {
+      upd_u = d["update_u"].cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+      upd_v = d["update_v"].cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+      if (upd_u.ndim() != 2 || upd_u.shape(0) != c.n || upd_u.shape(1) < 1 || upd_u.shape(1) > Device::kMaxRhs ||
+          upd_v.ndim() != 2 || upd_v.shape(0) != c.n || upd_v.shape(1) != upd_u.shape(1))
+        throw std::invalid_argument("update_u / update_v must be (n, k) arrays, 1 <= k <= 64");
+      c.update_u = upd_u.data();
+      c.update_v = upd_v.data();
+      c.update_k = upd_u.shape(1);
+    }
     RunReport r;
     {
       py::gil_scoped_release rel;
@@ -1193,6 +1273,14 @@ PYBIND11_MODULE(_C, mod) {
       o["race_count"] = r.race_count;
       o["races"] = r.races;
       o["race_ops"] = r.race_ops;
+    }
+    if (r.updated) {
+      py::dict u;
+      u["k"] = r.update.k;
+      u["min_pivot"] = r.update.min_pivot;
+      u["cond1"] = r.update.cond1;
+      u["seconds"] = r.update.seconds;
+      o["update"] = u;
     }
     if (r.rhs_solved) {
       o["axb_residual"] = r.rhs_residual;

@@ -367,5 +367,11 @@ void AsyncHostDevice::axpy_cols_masked(double* Y, int64_t ldy, const double* C_i
 void AsyncHostDevice::col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) {
   enqueue(s, [=] { inner_.col_abs_sum(dt, X, ldx, L, out, s); });
 }
+void AsyncHostDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw,
+                                  bool w_natural, const double* Z, int64_t ldz, int64_t k, double sign, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "rank_update: 1 <= k <= 64 columns");
+  g_last_rank_update_kernel = "host";
+  enqueue(s, [=] { inner_.rank_update(dt, X, ldx, L, W, ldw, w_natural, Z, ldz, k, sign, s); });
+}
 
 }  // namespace gj

@@ -440,5 +440,11 @@ void HipDevice::col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& 
   kern::col_abs_sum(dt, X, ldx, L, out, hs(streams_[s]));
   check_launch();
 }
+void HipDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw,
+                            bool w_natural, const double* Z, int64_t ldz, int64_t k, double sign, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "rank_update: 1 <= k <= 64 columns");
+  kern::rank_update(dt, X, ldx, L, W, ldw, w_natural, Z, ldz, k, sign, hs(streams_[s]));
+  check_launch();
+}
 
 }  // namespace gj

@@ -658,4 +658,23 @@ void HostDevice::col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout&
   });
 }
 
+void HostDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw,
+                             bool w_natural, const double* Z, int64_t ldz, int64_t k, double sign, int) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "rank_update: 1 <= k <= 64 columns");
+  g_last_rank_update_kernel = "host";
+  parallel_for(L.rows, nthreads_, [&](int64_t r) {
+    const int64_t g = L.global_row(r);
+    if (g >= L.n) return;
+    const double* w = W + (w_natural ? g : r) * ldw;
+    for (int64_t c = 0; c < L.n; ++c) {
+      double sum = 0.0;  // fp64 for both dtypes, then one rounding
+      for (int64_t j = 0; j < k; ++j) sum += w[j] * Z[c * ldz + j];
+      if (dt == DType::F64)
+        tp<double>(X)[r * ldx + c] += sign * sum;
+      else
+        tp<float>(X)[r * ldx + c] = (float)((double)tp<float>(X)[r * ldx + c] + sign * sum);
+    }
+  });
+}
+
 }  // namespace gj

@@ -809,5 +809,30 @@ void RaceCheckDevice::col_abs_sum(DType dt, const void* X, int64_t ldx, const La
   check(s, "col_abs_sum", {R(rect(X, ldx, L.n, real, (int64_t)dtype_size(dt)), "X"), W(span(out, 8 * L.n), "out")});
   inner_->col_abs_sum(dt, X, ldx, L, out, s);
 }
+void RaceCheckDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* Wm, int64_t ldw,
+                                  bool w_natural, const double* Z, int64_t ldz, int64_t k, double sign, int s) {
+  std::vector<Acc> a;
+  if (k >= 1 && k <= kMaxRhs) {  // (the inner device refuses any other k before it touches memory)
+    int64_t real = 0;  // the real local rows are a prefix: only the last global block row is short
+    for (int64_t b = 0; b < L.nblk; ++b)
+      real += std::max<int64_t>(0, std::min<int64_t>(L.m, L.n - L.global_block(b) * L.m));
+    if (w_natural) {  // W: the row blocks this rank owns
+      for (int64_t b = 0; b < L.nblk; ++b) {
+        const int64_t g0 = L.global_block(b) * L.m, h = std::min<int64_t>(L.m, L.n - g0);
+        if (h > 0) a.push_back(R(rect(Wm + g0 * ldw, ldw, k, h, 8), "W"));
+      }
+    } else if (real > 0) {
+      a.push_back(R(rect(Wm, ldw, k, real, 8), "W"));
+    }
+    a.push_back(R(rect(Z, ldz, k, L.n, 8), "Z"));
+    if (real > 0) {
+      const auto x = rect(X, ldx, L.n, real, (int64_t)dtype_size(dt));
+      a.push_back(R(x, "X"));
+      a.push_back(W(x, "X"));
+    }
+  }
+  check(s, "rank_update", a);
+  inner_->rank_update(dt, X, ldx, L, Wm, ldw, w_natural, Z, ldz, k, sign, s);
+}
 
 }  // namespace gj

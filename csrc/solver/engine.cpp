@@ -2493,6 +2493,121 @@ RhsBlockResult Engine::solve_rhs_block_trans_impl(const double* B, int64_t ldb, 
   return out;
 }
 
+// ---------------------------------------------------------------- inv(A + U V^T) from inv(A)
+UpdateResult Engine::update_inverse(const double* U, int64_t ldu, const double* V, int64_t ldv, int64_t k) {
+  return update_inverse_impl(U, ldu, V, ldv, k);
+}
+
+// (Device::copy2d takes host and device sources alike, as in solve_rhs_block_device)
+UpdateResult Engine::update_inverse_device(const double* U_dev, int64_t ldu, const double* V_dev, int64_t ldv,
+                                           int64_t k) {
+  return update_inverse_impl(U_dev, ldu, V_dev, ldv, k);
+}
+
+UpdateResult Engine::update_inverse_impl(const double* U, int64_t ldu, const double* V, int64_t ldv, int64_t k) {
+  GJ_REQUIRE(solved_, "update_inverse: solve() first");
+  GJ_REQUIRE(k >= 1 && k <= Device::kMaxRhs, "update_inverse: 1 <= k <= 64 columns (apply a larger update in pieces)");
+  GJ_REQUIRE(U && V && ldu >= k && ldv >= k, "update_inverse: U and V are n x k, ldu >= k and ldv >= k");
+  const auto t0 = std::chrono::steady_clock::now();
+  const int64_t n = L_.n, rows = L_.rows;
+  UpdateResult out;
+  out.k = k;
+  BufSet bufs(dev_);
+  const size_t nat = (size_t)std::max<int64_t>(n, 1) * k, loc = (size_t)std::max<int64_t>(rows, 1) * k;
+  double* Ud = bufs.get<double>(nat);    // U, V, Z = X^T V: natural row order, ld k
+  double* Vd = bufs.get<double>(nat);
+  double* Z = bufs.get<double>(nat);
+  double* Wl = bufs.get<double>(loc);    // this rank's rows of W = X U, then of W inv(C)
+  double* Wc = bufs.get<double>(loc);
+  double* Cd = bufs.get<double>((size_t)k * k);  // V^T X U, then inv(C)
+  dev_.copy2d(Ud, k * 8, U, ldu * 8, k * 8, n, S_MAIN);
+  dev_.copy2d(Vd, k * 8, V, ldv * 8, k * 8, n, S_MAIN);
+  dev_.panel_rhs(opt_.dtype, out_, L_.npad, L_, Ud, k, k, nullptr, k, Wl, k, 1.0, nullptr, nullptr, S_MAIN);
+  dev_.panel_rhs_t(opt_.dtype, out_, L_.npad, L_, Vd, k, k, Z, k, nullptr, S_MAIN);
+  comm_.allreduce_sum(dev_, Z, nat, DType::F64, S_MAIN);
+  // T = Z^T U = V^T X U, the same bits on every rank (Z and U are); C = I + T is formed on the host
+  dev_.gemm(DType::F64, GemmOp::Store, ALayout::KMajor, k, k, n, Z, k, Ud, k, Cd, k, S_MAIN);
+  std::vector<double> T((size_t)k * k);
+  dev_.copy(T.data(), Cd, sizeof(double) * (size_t)k * k, S_MAIN);
+  comm_.drain(dev_, S_MAIN);
+
+  // LU with partial pivoting of C in fp64; inv(C) column by column
+  double tmax = 0.0, c1 = 0.0;
+  for (double v : T) tmax = max_keep_nan(tmax, std::fabs(v));
+  const double scale = std::isfinite(tmax) ? std::max(1.0, tmax) : tmax;
+  std::vector<double> C(T);
+  for (int64_t i = 0; i < k; ++i) C[(size_t)(i * k + i)] += 1.0;
+  for (int64_t j = 0; j < k; ++j) {
+    double s = 0.0;
+    for (int64_t i = 0; i < k; ++i) s += std::fabs(C[(size_t)(i * k + j)]);
+    c1 = max_keep_nan(c1, s);
+  }
+  std::vector<int64_t> perm((size_t)k);
+  for (int64_t i = 0; i < k; ++i) perm[(size_t)i] = i;
+  bool singular = !std::isfinite(scale);
+  double minpiv = std::numeric_limits<double>::infinity();
+  for (int64_t c = 0; c < k && !singular; ++c) {
+    int64_t pr = c;
+    for (int64_t i = c + 1; i < k; ++i)
+      if (std::fabs(C[(size_t)(i * k + c)]) > std::fabs(C[(size_t)(pr * k + c)])) pr = i;
+    if (pr != c) {
+      for (int64_t j = 0; j < k; ++j) std::swap(C[(size_t)(c * k + j)], C[(size_t)(pr * k + j)]);
+      std::swap(perm[(size_t)c], perm[(size_t)pr]);
+    }
+    const double piv = C[(size_t)(c * k + c)];
+    if (!std::isfinite(piv) || std::fabs(piv) <= opt_.eps * scale) {
+      singular = true;
+      minpiv = std::isfinite(piv) ? std::min(minpiv, std::fabs(piv) / scale) : 0.0;
+      break;
+    }
+    minpiv = std::min(minpiv, std::fabs(piv) / scale);
+    for (int64_t i = c + 1; i < k; ++i) {
+      const double l = C[(size_t)(i * k + c)] / piv;
+      C[(size_t)(i * k + c)] = l;
+      for (int64_t j = c + 1; j < k; ++j) C[(size_t)(i * k + j)] -= l * C[(size_t)(c * k + j)];
+    }
+  }
+  std::vector<double> Ci((size_t)k * k, 0.0);
+  if (!singular) {
+    std::vector<double> y((size_t)k);
+    for (int64_t e = 0; e < k; ++e) {  // C x = e_e: L y = P e_e, U x = y
+      for (int64_t i = 0; i < k; ++i) {
+        double v = perm[(size_t)i] == e ? 1.0 : 0.0;
+        for (int64_t j = 0; j < i; ++j) v -= C[(size_t)(i * k + j)] * y[(size_t)j];
+        y[(size_t)i] = v;
+      }
+      for (int64_t i = k - 1; i >= 0; --i) {
+        double v = y[(size_t)i];
+        for (int64_t j = i + 1; j < k; ++j) v -= C[(size_t)(i * k + j)] * Ci[(size_t)(j * k + e)];
+        Ci[(size_t)(i * k + e)] = v / C[(size_t)(i * k + i)];
+      }
+    }
+    double ci1 = 0.0;
+    for (int64_t j = 0; j < k; ++j) {
+      double s = 0.0;
+      for (int64_t i = 0; i < k; ++i) s += std::fabs(Ci[(size_t)(i * k + j)]);
+      ci1 = max_keep_nan(ci1, s);
+    }
+    out.cond1 = c1 * ci1;
+    if (!std::isfinite(ci1)) singular = true;
+  }
+  out.min_pivot = minpiv;
+  // one outcome for all ranks, before anything is written
+  if (comm_.host_max(dev_, singular ? 1.0 : 0.0) > 0) {
+    out.status = Status::Singular;
+    out.cond1 = 0.0;
+    out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return out;
+  }
+  dev_.copy(Cd, Ci.data(), sizeof(double) * (size_t)k * k, S_MAIN);
+  if (rows > 0)
+    dev_.gemm(DType::F64, GemmOp::Store, ALayout::RowMajor, rows, k, k, Wl, k, Cd, k, Wc, k, S_MAIN);
+  dev_.rank_update(opt_.dtype, out_, L_.npad, L_, Wc, k, false, Z, k, k, -1.0, S_MAIN);
+  comm_.drain(dev_, S_MAIN);  // (Ci is read by the copy until here)
+  out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return out;
+}
+
 void SelfComm::host_allgather(Device&, const void* send, void* recv, size_t bytes) {
   if (send != recv) std::memcpy(recv, send, bytes);
 }

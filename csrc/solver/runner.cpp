@@ -138,6 +138,45 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
     if (rank == 0) sh.rep.stats = st;
     return;
   }
+  bool have_rows = src != nullptr;  // the fp64 rows of the matrix come from `local` (else the generator)
+  if (cfg.update_u && cfg.update_v) {
+    const int64_t k = cfg.update_k;
+    const UpdateResult ur = eng->update_inverse(cfg.update_u, k, cfg.update_v, k, k);
+    if (ur.status != Status::Ok) {
+      std::lock_guard<std::mutex> lk(sh.mu);
+      sh.rep.status = ur.status;
+      sh.rep.message = "singular update";
+      if (rank == 0) {
+        sh.rep.stats = st;
+        sh.rep.update = ur;
+      }
+      return;
+    }
+    // this rank's fp64 rows of A + U V^T
+    const int64_t real = eng->real_local_rows();
+    if (!src && real > 0) {
+      local.resize((size_t)real * cfg.n);
+      for (int64_t r = 0; r < real; ++r) {
+        const int64_t gr = L.global_row(r);
+        for (int64_t c = 0; c < cfg.n; ++c)
+          local[(size_t)(r * cfg.n + c)] = gen_value((int)cfg.gen.kind, cfg.gen.seed, cfg.n, gr, c);
+      }
+    }
+    for (int64_t r = 0; r < real; ++r) {
+      const double* u = cfg.update_u + L.global_row(r) * k;
+      for (int64_t c = 0; c < cfg.n; ++c) {
+        double sum = 0.0;
+        for (int64_t j = 0; j < k; ++j) sum += u[j] * cfg.update_v[c * k + j];
+        local[(size_t)(r * cfg.n + c)] += sum;
+      }
+    }
+    have_rows = true;
+    if (rank == 0) {
+      std::lock_guard<std::mutex> lk(sh.mu);
+      sh.rep.updated = true;
+      sh.rep.update = ur;
+    }
+  }
   if (cfg.want_corners) {
     auto c = eng->corner(nm, 1);
     if (rank == 0) {
@@ -159,7 +198,7 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
                  (cfg.ranks != 1 || cfg.gen.kind == GenKind::Hilbert));
   double res = 0;
   if (do_res) {
-    if (src) {
+    if (have_rows) {
       res = eng->residual_rows(local.data(), cfg.n);
     } else {
       res = eng->residual_generated(cfg.gen);
@@ -172,8 +211,8 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
     const auto t0 = std::chrono::steady_clock::now();
     const int refine = cfg.refine >= 0 ? cfg.refine : (cfg.solve.dtype == DType::F32 ? 10 : 2);
     if (src && local.empty()) load();  // the fp64 rows of A (residual_rows keeps them in `local`)
-    const RhsBlockResult br = eng->solve_rhs_block(sh.b.data(), k, x.data(), k, k, src ? nullptr : &cfg.gen,
-                                                   src ? local.data() : nullptr, nullptr, cfg.n, refine,
+    const RhsBlockResult br = eng->solve_rhs_block(sh.b.data(), k, x.data(), k, k, have_rows ? nullptr : &cfg.gen,
+                                                   have_rows ? local.data() : nullptr, nullptr, cfg.n, refine,
                                                    cfg.refine_tol, cfg.trans);
     const double tx = comm->host_max(
         *dev, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
@@ -206,8 +245,8 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
     const auto t0 = std::chrono::steady_clock::now();
     const int refine = cfg.refine >= 0 ? cfg.refine : (cfg.solve.dtype == DType::F32 ? 10 : 2);
     if (src && local.empty()) load();  // the fp64 rows of A (residual_rows keeps them in `local`)
-    const RhsResult rr = eng->solve_rhs(sh.b.data(), x.data(), src ? nullptr : &cfg.gen,
-                                        src ? local.data() : nullptr, cfg.n, refine, cfg.refine_tol);
+    const RhsResult rr = eng->solve_rhs(sh.b.data(), x.data(), have_rows ? nullptr : &cfg.gen,
+                                        have_rows ? local.data() : nullptr, cfg.n, refine, cfg.refine_tol);
     const double tx = comm->host_max(
         *dev, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     if (rank == 0) {

@@ -20,7 +20,8 @@ Python entry points:
 ``ops``                                kernel-level wrappers (tests, profiling)
 """
 from ._native import load_native, native_available, native_path  # noqa: F401
-from .models.gauss_jordan import Factored, GaussJordan, factor, inverse, run, solve  # noqa: F401
+from .models.gauss_jordan import (Factored, GaussJordan, SingularMatrixError, factor, inverse, run,  # noqa: F401
+                                 solve)
 from .parallel.dist import DistributedGaussJordan  # noqa: F401
 
 __version__ = "0.1.0"

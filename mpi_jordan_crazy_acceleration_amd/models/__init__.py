@@ -1,2 +1,3 @@
 """Solver "models": the block Gauss-Jordan inverter and the linear-system solver built on it."""
-from .gauss_jordan import Factored, GaussJordan, factor, inverse, run, solve  # noqa: F401
+from .gauss_jordan import (Factored, GaussJordan, SingularMatrixError, factor, inverse, run,  # noqa: F401
+                           solve)

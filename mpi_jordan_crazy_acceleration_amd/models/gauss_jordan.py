@@ -68,13 +68,17 @@ class GaussJordan:
     def run(self, n: int, gen: str = "absdiff", seed: int = 0, file: Optional[str] = None,
             input: Optional[np.ndarray] = None, keep_inverse: bool = False, repeats: int = 1,
             rhs=None, keep_solution: bool = False, profile: bool = False, nrhs: int = 1,
-            trans: bool = False) -> dict:
+            trans: bool = False, update=None) -> dict:
         """One CLI-equivalent run.  ``rhs``: None, "ones", "random", a file path, an n-vector or an
         n x k matrix — then x = inv(A) b is computed on the devices, refined in fp64, and
         ``axb_residual`` = ||A x - b||_inf reported.  ``nrhs`` > 1 (implied by a matrix): the block
         path, all columns per sweep (``axb_columns``: one info per column, ``x``: n x nrhs).
         ``trans``: A^T x = b from the same inverse (the block path at any width); ``axb_residual`` is
-        then ||A^T x - b||_inf and the report holds ``trans`` = True."""
+        then ||A^T x - b||_inf and the report holds ``trans`` = True.
+        ``update`` = (U, V), n-vectors or n x k with k <= 64: after the inversion the inverse is
+        updated to that of A + U V^T (Engine::update_inverse) and the ``rhs`` solve, the residual and
+        ``keep_inverse`` all refer to A + U V^T; the report gains ``update`` = {k, min_pivot, cond1,
+        seconds}."""
         cfg = self._cfg(n)
         cfg.update(gen=gen, seed=int(seed), keep_inverse=keep_inverse, repeats=int(repeats),
                    keep_solution=bool(keep_solution), profile=bool(profile))
@@ -92,6 +96,14 @@ class GaussJordan:
         cfg["nrhs"] = int(nrhs)
         if trans:
             cfg["trans"] = True
+        if update is not None:
+            u, v = (np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t, dtype=np.float64)
+                    for t in update)
+            u, v = u.reshape(u.shape[0], -1), v.reshape(v.shape[0], -1)
+            if u.shape != v.shape or u.shape[0] != int(n) or not 1 <= u.shape[1] <= 64:
+                raise ValueError("update=(U, V): n-vectors or n x k matrices of one shape, 1 <= k <= 64")
+            cfg["update_u"] = np.ascontiguousarray(u)
+            cfg["update_v"] = np.ascontiguousarray(v)
         rep = load_native().run_local(cfg)
         rep["status_name"] = STATUS.get(rep["status"], "error")
         return rep
@@ -195,13 +207,20 @@ class Factored:
     the object keeps in fp64); returns b's shape and type.  ``inverse()``: the inverse in A's type.
     ``n``, ``dtype`` ("fp64" | "fp32": the engine's arithmetic); ``infos``: the per-column refinement
     results of the last solve.  A CUDA tensor A stays on its GPU (the resident engine); a numpy
-    array or a CPU tensor runs one host rank."""
+    array or a CPU tensor runs one host rank.
+    ``update(U, V)``: the handle becomes that of A + U V^T (rank k <= 64) by the matrix inversion
+    lemma, one pass over the inverse instead of another inversion; ``updates`` counts the updates
+    applied since the inversion and ``last_update`` holds the last one's result."""
 
     def __init__(self, gj: "GaussJordan", A):
         self._is_torch = isinstance(A, torch.Tensor)
         self._like = A if self._is_torch else None
         self.dtype = gj.dtype
         self.infos: list = []
+        self.updates = 0
+        self.last_update: Optional[dict] = None
+        self._m = int(gj.block_size)
+        self._a64_owned = False
         if self._is_torch and A.is_cuda:
             self._cuda = True
             self._eng, self._a = gj._engine_resident(A)
@@ -244,6 +263,60 @@ class Factored:
             self.infos = list(infos)
         x = x.reshape(bn.shape)
         return torch.from_numpy(x).to(device=b.device, dtype=b.dtype) if b_torch else x
+
+    def update(self, U, V) -> dict:
+        """A <- A + U V^T: U and V are n-vectors (k = 1, Sherman-Morrison) or n x k with k <= 64 (else
+        ValueError; apply a larger update in pieces), numpy arrays or torch tensors.  The engine's
+        inverse becomes inv(A + U V^T) = X - (X U) inv(I + V^T X U) (V^T X) (Engine::update_inverse) and
+        the kept fp64 rows become A + U V^T, so ``solve`` and ``inverse`` go on unchanged.  Returns
+        {k, min_pivot, cond1, seconds}: the smallest pivot (relative) and the 1-norm condition number
+        of the k x k capacitance matrix I + V^T X U -- a near-singular update is accepted and shows
+        there (and in the ``converged`` flags of later solves).  A singular one raises
+        SingularMatrixError and leaves the handle as it was."""
+        def as2d(M):
+            if isinstance(M, torch.Tensor):
+                t = M.detach().to(torch.float64)
+                t = t if self._cuda else t.cpu()
+            else:
+                t = torch.as_tensor(np.asarray(M, dtype=np.float64))
+            if t.ndim == 1:
+                t = t.reshape(-1, 1)
+            if t.ndim != 2 or t.shape[0] != self.n or t.shape[1] < 1:
+                raise ValueError("U and V must be n-vectors or n x k matrices")
+            return t
+
+        u, v = as2d(U), as2d(V)
+        if u.shape != v.shape:
+            raise ValueError("U and V must have the same shape")
+        k = int(u.shape[1])
+        if k > 64:
+            raise ValueError("update: at most 64 columns at a time; apply a larger update in pieces")
+        if self._cuda:
+            dev = self._a64.device
+            u, v = u.to(dev).contiguous(), v.to(dev).contiguous()
+            torch.cuda.synchronize(dev)
+            info = self._eng.update_inverse(u_dev=u.data_ptr(), ldu=u.stride(0), v_dev=v.data_ptr(),
+                                            ldv=v.stride(0), ncols=k)
+        else:
+            un, vn = np.ascontiguousarray(u.numpy()), np.ascontiguousarray(v.numpy())
+            info = self._eng.update_inverse(un, vn)
+        if info["status"] == 1:
+            raise SingularMatrixError("singular update: I + V^T inv(A) U is singular")
+        if info["status"] != 0:
+            raise RuntimeError(STATUS.get(info["status"], "error"))
+        # (the kept rows may be the caller's own array until the first update: never written in place)
+        if self._cuda:  # A's fp64 rows stay on the GPU: A += U V^T by the same kernel
+            from ..ops import rank_update
+            if not self._a64_owned:
+                self._a64 = self._a64.clone()
+            rank_update(self._a64, u, v, self.n, self._m, sign=1.0, w_natural=True)
+        else:
+            self._a64 = self._a64 + un @ vn.T
+        self._a64_owned = True
+        res = {key: info[key] for key in ("k", "min_pivot", "cond1", "seconds")}
+        self.updates += 1
+        self.last_update = res
+        return res
 
     def inverse(self):
         if self._cuda:

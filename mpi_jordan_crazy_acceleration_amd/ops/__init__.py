@@ -261,6 +261,22 @@ def panel_rhs_t(P: torch.Tensor, V: torch.Tensor, S: torch.Tensor, n: int, m: in
     return S
 
 
+def rank_update(X: torch.Tensor, W: torch.Tensor, Z: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0,
+                sign: float = 1.0, w_natural: bool = False, ncols: int = None) -> torch.Tensor:
+    """X[r, c] += sign * sum_j W[wrow(r), j] * Z[c, j] over this rank's real local rows r and the columns
+    c < n, in place (Device::rank_update): the sum in fp64, added to the widened element and rounded
+    once to X's dtype.  ``X`` this rank's rows of a panel (fp64 / fp32, rows x >= n), ``W`` fp64 in
+    local row order (``w_natural`` False: wrow(r) = r, what panel_rhs writes) or n x ncols in natural
+    order (True: wrow(r) = the global row of r), ``Z`` fp64, n x ncols in natural order, ``sign`` +1 or
+    -1.  Padding rows, columns >= n and pitch gaps of X are neither read nor written.  Views with unit
+    column stride; ``ncols`` defaults to Z's width (1..64, else an error)."""
+    assert W.dtype == Z.dtype == torch.float64 and X.stride(-1) == 1 and W.stride(-1) == 1 and Z.stride(-1) == 1
+    ncols = Z.shape[1] if ncols is None else int(ncols)
+    device_for(X).rank_update(_DT[X.dtype], _p(X), X.stride(0), n, m, p, k, _p(W), W.stride(0), bool(w_natural),
+                              _p(Z), Z.stride(0), ncols, float(sign))
+    return X
+
+
 def axpy_cols_masked(Y: torch.Tensor, S: torch.Tensor, C_in: torch.Tensor = None, sign: float = 1.0,
                      active: torch.Tensor = None, colmax: torch.Tensor = None, ncols: int = None) -> torch.Tensor:
     """Y[:, j] = C_in[:, j] + sign * S[:, j] for the columns with active[j] != 0 (Device::axpy_cols_masked;

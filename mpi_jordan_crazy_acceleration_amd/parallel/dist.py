@@ -230,6 +230,28 @@ class DistributedGaussJordan:
                                                   tol=float(tol), trans=bool(trans))
         return x.reshape(B.shape), list(infos)
 
+    def update(self, U: np.ndarray, V: np.ndarray) -> dict:
+        """Collective, after solve(): the resident inverse becomes that of A + U V^T
+        (Engine::update_inverse), U and V n-vectors or n x k (k <= 64, else ValueError), the same on
+        every rank.  Returns {k, min_pivot, cond1, seconds}; a singular update raises
+        SingularMatrixError on every rank with the inverse unchanged.  The engine does not hold A:
+        later ``solve_rhs(..., A_rows=)`` / ``residual`` calls are given the rows of A + U V^T."""
+        from ..models.gauss_jordan import STATUS, SingularMatrixError
+
+        u = np.asarray(U, dtype=np.float64)
+        v = np.asarray(V, dtype=np.float64)
+        if u.shape != v.shape or u.ndim not in (1, 2) or u.shape[0] != self.n:
+            raise ValueError("U and V must be n-vectors or n x k matrices of one shape")
+        u, v = np.ascontiguousarray(u.reshape(self.n, -1)), np.ascontiguousarray(v.reshape(self.n, -1))
+        if not 1 <= u.shape[1] <= 64:
+            raise ValueError("update: 1 <= k <= 64 columns at a time; apply a larger update in pieces")
+        info = self.engine.update_inverse(u, v)
+        if info["status"] == 1:
+            raise SingularMatrixError("singular update: I + V^T inv(A) U is singular")
+        if info["status"] != 0:
+            raise RuntimeError(STATUS.get(info["status"], "error"))
+        return {key: info[key] for key in ("k", "min_pivot", "cond1", "seconds")}
+
     # ---- output
     def local_rows(self) -> np.ndarray:
         return self.engine.download_local_rows()
