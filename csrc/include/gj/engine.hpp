@@ -192,6 +192,8 @@ class Engine {
   double residual_file(const std::string& path, int nthreads = 0, Status* status = nullptr);
 
   // ---- A x = b (BASELINE config 1; SURVEY.md §5.6 --rhs) ----
+  // Everything from here to update_inverse_device works from the resident inverse and lives in
+  // solver/refine.cpp; the column rule of all three solve paths is its ColumnRule, once.
   // x = inv(A) b from the result panel: one MFMA GEMV per rank + all-gather (collective).
   // b and x are full n-vectors on every rank.
   void apply_inverse(const double* b, double* x);
@@ -316,13 +318,18 @@ class Engine {
   SolveStats solve_steps();
   RhsResult solve_rhs_impl(const double* b, double* x, const GenSpec* gen, const double* host_rows,
                            const void* dev_rows, int64_t ld, int max_refine, double tol);
+  // The block driver of both solve_rhs_block paths (refine.cpp): the column-group loop and the column
+  // rule are its own; what A X = B and A^T X = B differ in (the products, the buffers of the iterate,
+  // how the column norms become global, ||A||_inf or ||A||_1) comes from a BlockPath.
+  struct BlockPath;
+  void block_path_plain(BlockPath& f, const double* Aw, int64_t kw);
+  void block_path_trans(BlockPath& f, const double* Aw, int64_t kw);
   RhsBlockResult solve_rhs_block_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                       bool on_device, const GenSpec* gen, const double* host_rows,
-                                      const void* dev_rows, int64_t ld, int max_refine, double tol);
-  UpdateResult update_inverse_impl(const double* U, int64_t ldu, const double* V, int64_t ldv, int64_t k);
-  RhsBlockResult solve_rhs_block_trans_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
-                                            bool on_device, const GenSpec* gen, const double* host_rows,
-                                            const void* dev_rows, int64_t ld, int max_refine, double tol);
+                                      const void* dev_rows, int64_t ld, int max_refine, double tol, bool trans);
+  // This rank's rows of A in fp64 (ld npad) from the generator, an fp64 device array or host rows;
+  // enqueued on MAIN, not waited for.
+  void stage_rows_f64(double* Aw, const GenSpec* gen, const double* host_rows, const void* dev_rows, int64_t ld);
   // GJ_VERIFY (SolveOptions::verify): hash slots of a panel, (d*C + 3d + 1) + 3 (2d + 2) of them:
   //   [chunk c][step j] Rb segment at MAIN's chunk update | pp[j] panel piece at its first consumer
   //   | la[j] look-ahead row segment at the look-ahead update | recs[j] gathered pivot records |

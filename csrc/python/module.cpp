@@ -175,6 +175,11 @@ static py::dict rhs_info(const RhsResult& rr) {
   return info;
 }
 
+// max_refine < 0: the default budget of refinement steps, by the engine dtype
+static int refine_budget(const Engine& eng, int max_refine) {
+  return max_refine >= 0 ? max_refine : eng.options().dtype == DType::F64 ? 2 : 10;
+}
+
 PYBIND11_MODULE(_C, mod) {
   mod.doc() = "MI355X-native block Gauss-Jordan inversion: native engine, HIP kernels, RCCL comm";
 
@@ -933,7 +938,7 @@ PYBIND11_MODULE(_C, mod) {
              const int64_t n = e.eng->layout().n;
              if (b.ndim() != 1 || b.shape(0) != n) throw std::invalid_argument("b must be an n-vector");
              if (ld < n) throw std::invalid_argument("ld < n");
-             if (max_refine < 0) max_refine = e.eng->options().dtype == DType::F64 ? 2 : 10;
+             max_refine = refine_budget(*e.eng, max_refine);
              py::array_t<double> x(n);
              RhsResult rr;
              {
@@ -941,13 +946,7 @@ PYBIND11_MODULE(_C, mod) {
                rr = e.eng->solve_rhs_device(b.data(), x.mutable_data(), reinterpret_cast<const void*>(rows), ld,
                                             max_refine, tol);
              }
-             py::dict info;
-             info["residual"] = rr.residual;
-             info["backward_error"] = rr.backward_error;
-             info["history"] = rr.history;
-             info["steps"] = rr.steps;
-             info["converged"] = rr.converged;
-             return py::make_tuple(x, info);
+             return py::make_tuple(x, rhs_info(rr));
            },
            py::arg("b"), py::arg("rows_f64"), py::arg("ld"), py::arg("max_refine") = -1, py::arg("tol") = 1e-15,
            "A x = b after solve(): x = inv(A) b by the native GEMV, refined in fp64 against this rank's rows "
@@ -957,7 +956,7 @@ PYBIND11_MODULE(_C, mod) {
               uintptr_t b_dev, int64_t ldb, uintptr_t x_dev, int64_t ldx, int64_t ncols, int max_refine,
               double tol, bool trans) {
              const int64_t n = e.eng->layout().n;
-             if (max_refine < 0) max_refine = e.eng->options().dtype == DType::F64 ? 2 : 10;
+             max_refine = refine_budget(*e.eng, max_refine);
              GenSpec g;
              const GenSpec* gp = nullptr;
              if (!gen.is_none()) {
@@ -1058,7 +1057,7 @@ PYBIND11_MODULE(_C, mod) {
              if (b.ndim() != 1 || b.shape(0) != n) throw std::invalid_argument("b must be an n-vector");
              if (rows.ndim() != 2 || rows.shape(0) != e.eng->real_local_rows() || rows.shape(1) != n)
                throw std::invalid_argument("rows must be (real_rows, n) float64");
-             if (max_refine < 0) max_refine = e.eng->options().dtype == DType::F64 ? 2 : 10;
+             max_refine = refine_budget(*e.eng, max_refine);
              py::array_t<double> x(n);
              RhsResult rr;
              {
@@ -1075,7 +1074,7 @@ PYBIND11_MODULE(_C, mod) {
               py::array_t<double, py::array::c_style | py::array::forcecast> b, int max_refine, double tol) {
              const int64_t n = e.eng->layout().n;
              if (b.ndim() != 1 || b.shape(0) != n) throw std::invalid_argument("b must be an n-vector");
-             if (max_refine < 0) max_refine = e.eng->options().dtype == DType::F64 ? 2 : 10;
+             max_refine = refine_budget(*e.eng, max_refine);
              GenSpec g;
              g.kind = parse_gen(kind);
              g.seed = seed;
@@ -1085,13 +1084,7 @@ PYBIND11_MODULE(_C, mod) {
                py::gil_scoped_release rel;
                rr = e.eng->solve_rhs(b.data(), x.mutable_data(), &g, nullptr, 0, max_refine, tol);
              }
-             py::dict info;
-             info["residual"] = rr.residual;
-             info["backward_error"] = rr.backward_error;
-             info["history"] = rr.history;
-             info["steps"] = rr.steps;
-             info["converged"] = rr.converged;
-             return py::make_tuple(x, info);
+             return py::make_tuple(x, rhs_info(rr));
            },
            py::arg("kind"), py::arg("seed"), py::arg("b"), py::arg("max_refine") = -1, py::arg("tol") = 1e-15,
            "A x = b after solve() of the generated matrix (kind, seed): x = inv(A) b, refined in fp64 against A "

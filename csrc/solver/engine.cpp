@@ -1961,653 +1961,6 @@ double Engine::residual_rows(const double* host, int64_t ld) {
   return residual_common(X_, false);
 }
 
-// ---------------------------------------------------------------- A x = b
-namespace {
-// full n-vector (double, host) -> padded device vector of the engine dtype
-void* upload_vector(Device& dev, DType dt, const double* v, int64_t n, int64_t npad) {
-  double* st = static_cast<double*>(dev.alloc(sizeof(double) * npad));
-  dev.memset0(st, sizeof(double) * npad, S_MAIN);
-  dev.copy(st, v, sizeof(double) * n, S_MAIN);
-  void* d = dev.alloc(dtype_size(dt) * npad);
-  dev.upload_convert(dt, d, 1, st, 1, npad, 1, S_MAIN);
-  dev.sync_stream(S_MAIN);
-  dev.release(st);
-  return d;
-}
-}  // namespace
-
-// local product y = P * v  (P: this rank's rows of a panel, v: full padded vector) -> host doubles
-static std::vector<double> local_matvec(Device& dev, DType dt, const void* P, const Layout& L,
-                                        const void* vd) {
-  const size_t es = dtype_size(dt);
-  std::vector<double> y((size_t)L.rows, 0.0);
-  if (L.rows == 0) return y;
-  void* yd = dev.alloc(es * L.rows);
-  dev.gemm(dt, GemmOp::Store, ALayout::RowMajor, L.rows, 1, L.npad, P, L.npad, vd, 1, yd, 1, S_MAIN);
-  std::vector<char> h(es * L.rows);
-  dev.copy(h.data(), yd, es * L.rows, S_MAIN);
-  dev.sync_stream(S_MAIN);
-  dev.release(yd);
-  for (int64_t i = 0; i < L.rows; ++i)
-    y[i] = dt == DType::F64 ? reinterpret_cast<double*>(h.data())[i] : (double)reinterpret_cast<float*>(h.data())[i];
-  return y;
-}
-
-void Engine::apply_inverse(const double* b, double* x) {
-  GJ_REQUIRE(solved_, "apply_inverse: solve() first");
-  const int64_t m = L_.m, n = L_.n, p = L_.p;
-  void* bd = upload_vector(dev_, opt_.dtype, b, n, L_.npad);
-  std::vector<double> mine = local_matvec(dev_, opt_.dtype, out_, L_, bd);
-  dev_.release(bd);
-  const int64_t per = L_.max_nblk * m;
-  mine.resize((size_t)per, 0.0);
-  std::vector<double> all((size_t)per * p);
-  comm_.host_allgather(dev_, mine.data(), all.data(), sizeof(double) * per);
-  for (int64_t q = 0; q < p; ++q)
-    for (int64_t j = 0; j < rows_owned(L_.Nr, p, q); ++j)
-      for (int64_t r = 0; r < m; ++r) {
-        const int64_t gi = (j * p + q) * m + r;
-        if (gi < n) x[gi] = all[(size_t)q * per + j * m + r];
-      }
-}
-
-double Engine::axb_residual(const double* x, const double* b) {
-  const int64_t m = L_.m, n = L_.n;
-  void* xd = upload_vector(dev_, opt_.dtype, x, n, L_.npad);
-  std::vector<double> y = local_matvec(dev_, opt_.dtype, X_, L_, xd);
-  dev_.release(xd);
-  double local = 0.0;
-  for (int64_t i = 0; i < L_.rows; ++i) {
-    const int64_t gi = L_.global_block(i / m) * m + i % m;
-    if (gi < n) local = std::max(local, std::fabs(y[i] - b[gi]));
-  }
-  return comm_.host_max(dev_, local);
-}
-
-// x = inv(A) b, then iterative refinement with the residual in fp64:
-//   r_k = b - A x_k  (A in fp64: regenerated, or re-uploaded from the caller's fp64 rows;
-//                     fp64 MFMA GEMV, the full vector all-gathered)
-//   x_{k+1} = x_k + X r_k   (X = the computed inverse, engine dtype)
-// It converges when ||I - X A|| < 1; each step gains about -log10 ||I - X A|| digits.  Stops at
-// the normwise backward error ||r|| / (||A|| ||x|| + ||b||) <= tol (inf-norms), after max_refine
-// steps, or when the residual stops shrinking
-// (refinement cannot converge: reported, not hidden).
-RhsResult Engine::solve_rhs_device(const double* b, double* x, const void* dev_rows_f64, int64_t ld,
-                                   int max_refine, double tol) {
-  GJ_REQUIRE(dev_rows_f64 || real_local_rows() == 0, "solve_rhs_device: the matrix rows are needed");
-  return solve_rhs_impl(b, x, nullptr, nullptr, dev_rows_f64, ld, max_refine, tol);
-}
-
-RhsResult Engine::solve_rhs(const double* b, double* x, const GenSpec* gen, const double* host_rows,
-                            int64_t ld, int max_refine, double tol) {
-  GJ_REQUIRE(gen || host_rows || real_local_rows() == 0,
-             "solve_rhs: the matrix (generator or rows) is needed for the fp64 residual");
-  return solve_rhs_impl(b, x, gen, host_rows, nullptr, ld, max_refine, tol);
-}
-
-RhsResult Engine::solve_rhs_impl(const double* b, double* x, const GenSpec* gen, const double* host_rows,
-                                 const void* dev_rows, int64_t ld, int max_refine, double tol) {
-  GJ_REQUIRE(solved_, "solve_rhs: solve() first");
-  const int64_t m = L_.m, n = L_.n;
-  RhsResult rr;
-  void* Aw = dev_.alloc((size_t)std::max<int64_t>(L_.rows, 1) * L_.npad * 8);
-  try {
-    if (gen) {
-      dev_.generate(DType::F64, Aw, L_, *gen, S_MAIN);
-    } else if (dev_rows) {  // zero + identity padding, then the real rows device-to-device
-      GenSpec z;
-      z.kind = GenKind::Zero;
-      dev_.generate(DType::F64, Aw, L_, z, S_MAIN);
-      const int64_t real = real_local_rows();
-      if (real > 0) dev_.copy2d(Aw, L_.npad * 8, dev_rows, ld * 8, n * 8, real, S_MAIN);
-    } else {
-      upload_rows_into(Aw, DType::F64, host_rows, ld);
-    }
-    dev_.sync_stream(S_MAIN);
-    double bn = 0;
-    for (int64_t i = 0; i < n; ++i) bn = std::max(bn, std::fabs(b[i]));
-    if (bn == 0) bn = 1;
-    dev_.row_abs_max(DType::F64, Aw, L_.npad, L_, dscratch_, S_MAIN);  // ||A||_inf (fp64)
-    dev_.copy(dhost_, dscratch_, sizeof(double), S_MAIN);
-    dev_.sync_stream(S_MAIN);
-    const double an = comm_.host_max(dev_, L_.nblk > 0 ? dhost_[0] : 0.0);
-    apply_inverse(b, x);
-    std::vector<double> r((size_t)n), d((size_t)n);
-    // the best iterate so far (a diverging refinement, e.g. an fp32 inverse with ||I - XA|| near 1,
-    // must not hand back a worse x than it was given)
-    std::vector<double> best_x(x, x + n);
-    RhsResult best;
-    double best_rn = 1e300;
-    double prev = 1e300;
-    for (int it = 0;; ++it) {
-      // r = b - A x (this rank's rows, fp64), all-gathered to the full vector
-      void* xd = upload_vector(dev_, DType::F64, x, n, L_.npad);
-      std::vector<double> y = local_matvec(dev_, DType::F64, Aw, L_, xd);
-      dev_.release(xd);
-      const int64_t per = L_.max_nblk * m;
-      std::vector<double> mine((size_t)per, 0.0), all((size_t)per * L_.p);
-      for (int64_t i = 0; i < L_.rows; ++i) {
-        const int64_t gi = L_.global_block(i / m) * m + i % m;
-        if (gi < n) mine[(size_t)i] = b[gi] - y[(size_t)i];
-      }
-      comm_.host_allgather(dev_, mine.data(), all.data(), sizeof(double) * per);
-      double rn = 0;
-      for (int64_t q = 0; q < L_.p; ++q)
-        for (int64_t j = 0; j < rows_owned(L_.Nr, L_.p, q); ++j)
-          for (int64_t e = 0; e < m; ++e) {
-            const int64_t gi = (j * L_.p + q) * m + e;
-            if (gi < n) {
-              r[(size_t)gi] = all[(size_t)q * per + j * m + e];
-              rn = std::max(rn, std::fabs(r[(size_t)gi]));
-            }
-          }
-      double xn = 0;
-      for (int64_t i = 0; i < n; ++i) xn = std::max(xn, std::fabs(x[i]));
-      rr.history.push_back(rn / bn);
-      rr.residual = rn;
-      rr.backward_error = rn / (an * xn + bn);
-      if (rr.backward_error <= tol) {
-        rr.converged = true;
-        break;
-      }
-      if (rn < best_rn) {
-        best_rn = rn;
-        best_x.assign(x, x + n);
-        best = rr;
-      }
-      if (it >= max_refine || (it > 0 && rn > 0.5 * prev)) {  // budget spent / not contracting
-        if (rn > best_rn) {  // return the best iterate, with its own residual (history kept)
-          std::copy(best_x.begin(), best_x.end(), x);
-          best.history = rr.history;
-          rr = best;
-        }
-        break;
-      }
-      prev = rn;
-      apply_inverse(r.data(), d.data());
-      for (int64_t i = 0; i < n; ++i) x[i] += d[(size_t)i];
-      rr.steps = it + 1;
-    }
-  } catch (...) {
-    dev_.release(Aw);
-    throw;
-  }
-  dev_.release(Aw);
-  return rr;
-}
-
-// ---------------------------------------------------------------- A X = B, a block of columns
-RhsBlockResult Engine::solve_rhs_block(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
-                                       const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
-                                       int64_t ld, int max_refine, double tol, bool trans) {
-  if (trans)
-    return solve_rhs_block_trans_impl(B, ldb, X, ldx, k, false, gen, host_rows, dev_rows_f64, ld, max_refine, tol);
-  return solve_rhs_block_impl(B, ldb, X, ldx, k, false, gen, host_rows, dev_rows_f64, ld, max_refine, tol);
-}
-
-RhsBlockResult Engine::solve_rhs_block_device(const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx,
-                                              int64_t k, const GenSpec* gen, const double* host_rows,
-                                              const void* dev_rows_f64, int64_t ld, int max_refine, double tol,
-                                              bool trans) {
-  if (trans)
-    return solve_rhs_block_trans_impl(B_dev, ldb, X_dev, ldx, k, true, gen, host_rows, dev_rows_f64, ld, max_refine,
-                                      tol);
-  return solve_rhs_block_impl(B_dev, ldb, X_dev, ldx, k, true, gen, host_rows, dev_rows_f64, ld, max_refine, tol);
-}
-
-namespace {
-// device / pinned buffers of one call, released together (after the device went idle)
-struct BufSet {
-  Device& dev;
-  std::vector<void*> mem, pinned;
-  explicit BufSet(Device& d) : dev(d) {}
-  template <typename T>
-  T* get(size_t count, bool zero = true) {
-    const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
-    void* p = dev.alloc(bytes);
-    mem.push_back(p);
-    if (zero) dev.memset0(p, bytes, S_MAIN);
-    return static_cast<T*>(p);
-  }
-  template <typename T>
-  T* get_pinned(size_t count) {
-    void* p = dev.alloc_pinned(sizeof(T) * std::max<size_t>(count, 1));
-    pinned.push_back(p);
-    return static_cast<T*>(p);
-  }
-  ~BufSet() {
-    try {
-      dev.sync_all();
-    } catch (...) {
-    }
-    for (void* p : mem) dev.release(p);
-    for (void* p : pinned) dev.release_pinned(p);
-  }
-};
-}  // namespace
-
-RhsBlockResult Engine::solve_rhs_block_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
-                                            bool on_device, const GenSpec* gen, const double* host_rows,
-                                            const void* dev_rows, int64_t ld, int max_refine, double tol) {
-  GJ_REQUIRE(solved_, "solve_rhs_block: solve() first");
-  GJ_REQUIRE(k >= 1 && ldb >= k && ldx >= k, "solve_rhs_block: k >= 1 columns, ldb >= k and ldx >= k");
-  GJ_REQUIRE(gen || host_rows || dev_rows || real_local_rows() == 0,
-             "solve_rhs_block: the matrix (generator or rows) is needed for the fp64 residual");
-  const auto t0 = std::chrono::steady_clock::now();
-  const int64_t m = L_.m, n = L_.n, p = L_.p;
-  const int64_t kw = std::min<int64_t>(k, Device::kMaxRhs);  // widest group = every buffer's leading dimension
-  const int64_t per = L_.max_nblk * m;                       // rows every rank sends to an all-gather
-  RhsBlockResult out;
-  out.col.resize((size_t)k);
-  BufSet bufs(dev_);
-  // A's local rows in fp64, once per call
-  double* Aw = bufs.get<double>((size_t)std::max<int64_t>(L_.rows, 1) * L_.npad, false);
-  if (gen) {
-    dev_.generate(DType::F64, Aw, L_, *gen, S_MAIN);
-  } else if (dev_rows) {  // zero + identity padding, then the real rows device-to-device
-    GenSpec z;
-    z.kind = GenKind::Zero;
-    dev_.generate(DType::F64, Aw, L_, z, S_MAIN);
-    const int64_t real = real_local_rows();
-    if (real > 0) dev_.copy2d(Aw, L_.npad * 8, dev_rows, ld * 8, n * 8, real, S_MAIN);
-  } else {
-    upload_rows_into(Aw, DType::F64, host_rows, ld);
-  }
-  dev_.row_abs_max(DType::F64, Aw, L_.npad, L_, dscratch_, S_MAIN);  // ||A||_inf (fp64)
-  dev_.copy(dhost_, dscratch_, sizeof(double), S_MAIN);
-  dev_.sync_stream(S_MAIN);
-  const double an = comm_.host_max(dev_, L_.nblk > 0 ? dhost_[0] : 0.0);
-
-  const size_t loc = (size_t)per * kw, nat = (size_t)std::max<int64_t>(n, 1) * kw;
-  double* Vb = bufs.get<double>(nat);     // B, natural row order
-  double* Vx = bufs.get<double>(nat);     // the iterate X, natural row order
-  double* Vr = bufs.get<double>(nat);     // the residual R, natural row order
-  double* Bloc = bufs.get<double>(loc);   // this rank's rows of B / X / R / the best iterate
-  double* Xloc = bufs.get<double>(loc);
-  double* Rloc = bufs.get<double>(loc);
-  double* best = bufs.get<double>(loc);
-  double* gath = bufs.get<double>(loc * (size_t)p);
-  double* dnorm = bufs.get<double>(2 * Device::kMaxRhs);   // ||r_j|| | ||x_j|| (this rank's rows)
-  int32_t* dflag = bufs.get<int32_t>(2 * Device::kMaxRhs);  // active | save-mask
-  double* hnorm = bufs.get_pinned<double>(2 * Device::kMaxRhs);
-  int32_t* hflag = bufs.get_pinned<int32_t>(2 * Device::kMaxRhs);
-  std::vector<double> hb;  // a device-resident B's columns on the host, for ||b_j|| only
-  std::vector<double> mine, all((size_t)(2 * Device::kMaxRhs) * p);
-
-  auto gather_natural = [&](double* dst, const double* src_loc) {
-    comm_.allgather(dev_, src_loc, gath, loc * sizeof(double), S_MAIN);
-    dev_.gather_rows_natural(dst, kw, gath, kw, L_, kw, S_MAIN);
-  };
-
-  for (int64_t c0 = 0; c0 < k; c0 += kw) {
-    const int64_t kg = std::min<int64_t>(kw, k - c0);
-    // B's columns of this group: natural order on the device, this rank's rows of it, ||b_j||
-    dev_.copy2d(Vb, kw * 8, B + c0, ldb * 8, kg * 8, n, S_MAIN);
-    for (int64_t b = 0; b < L_.nblk; ++b) {
-      const int64_t g0 = L_.global_block(b) * m;
-      if (g0 < n)
-        dev_.copy(Bloc + b * m * kw, Vb + g0 * kw, sizeof(double) * (size_t)(std::min<int64_t>(m, n - g0) * kw),
-                  S_MAIN);
-    }
-    std::vector<double> bn((size_t)kg, 0.0);
-    const double* bh = B + c0;
-    int64_t ldh = ldb;
-    if (on_device) {
-      hb.resize((size_t)n * kw);
-      dev_.copy(hb.data(), Vb, sizeof(double) * (size_t)n * kw, S_MAIN);
-      dev_.sync_stream(S_MAIN);
-      bh = hb.data();
-      ldh = kw;
-    }
-    for (int64_t i = 0; i < n; ++i)
-      for (int64_t j = 0; j < kg; ++j) bn[(size_t)j] = std::max(bn[(size_t)j], std::fabs(bh[i * ldh + j]));
-    for (double& v : bn)
-      if (v == 0) v = 1;
-
-    // x_0 = inv(A) b in the engine dtype, every column active
-    dev_.host_access(hflag, sizeof(int32_t) * 2 * Device::kMaxRhs, true);
-    for (int64_t j = 0; j < Device::kMaxRhs; ++j) hflag[j] = j < kg ? 1 : 0;
-    dev_.copy(dflag, hflag, sizeof(int32_t) * Device::kMaxRhs, S_MAIN);
-    dev_.panel_rhs(opt_.dtype, out_, L_.npad, L_, Vb, kw, kg, nullptr, 0, Xloc, kw, 1.0, nullptr,
-                   dnorm + Device::kMaxRhs, S_MAIN);
-    gather_natural(Vx, Xloc);
-
-    std::vector<int> active((size_t)kg, 1);
-    std::vector<double> best_rn((size_t)kg, 1e300), prev((size_t)kg, 1e300);
-    std::vector<RhsResult> bestr((size_t)kg);
-    RhsResult* rr = out.col.data() + c0;
-    for (int it = 0;; ++it) {
-      // r = b - A x on this rank's rows (fp64), then the whole residual on every rank
-      dev_.panel_rhs(DType::F64, Aw, L_.npad, L_, Vx, kw, kg, Bloc, kw, Rloc, kw, -1.0, dflag, dnorm, S_MAIN);
-      gather_natural(Vr, Rloc);
-      dev_.copy(hnorm, dnorm, sizeof(double) * 2 * Device::kMaxRhs, S_MAIN);
-      comm_.drain(dev_, S_MAIN);
-      dev_.host_access(hnorm, sizeof(double) * 2 * Device::kMaxRhs, false);
-      // the column norms over all ranks (a NaN from any rank wins)
-      mine.assign(hnorm, hnorm + 2 * Device::kMaxRhs);
-      comm_.host_allgather(dev_, mine.data(), all.data(), sizeof(double) * mine.size());
-      for (int64_t q = 0; q < p; ++q)
-        for (size_t e = 0; e < mine.size(); ++e)
-          mine[e] = q == 0 ? all[e] : max_keep_nan(mine[e], all[(size_t)q * mine.size() + e]);
-      out.sweeps = std::max(out.sweeps, it + 1);
-      // the per-column decision of solve_rhs
-      dev_.host_access(hflag, sizeof(int32_t) * 2 * Device::kMaxRhs, true);
-      bool any = false;
-      for (int64_t j = 0; j < kg; ++j) {
-        int32_t save = 0;
-        if (active[(size_t)j]) {
-          const double rn = mine[(size_t)j], xn = mine[(size_t)(Device::kMaxRhs + j)];
-          RhsResult& r = rr[j];
-          r.history.push_back(rn / bn[(size_t)j]);
-          r.residual = rn;
-          r.backward_error = rn / (an * xn + bn[(size_t)j]);
-          if (r.backward_error <= tol) {
-            r.converged = true;
-            active[(size_t)j] = 0;
-            save = 1;
-          } else {
-            if (rn < best_rn[(size_t)j]) {
-              best_rn[(size_t)j] = rn;
-              bestr[(size_t)j] = r;
-              save = 1;
-            }
-            if (it >= max_refine || (it > 0 && rn > 0.5 * prev[(size_t)j])) {  // budget spent / not contracting
-              if (rn > best_rn[(size_t)j]) {  // the best iterate (already saved), with its own residual
-                bestr[(size_t)j].history = r.history;
-                r = bestr[(size_t)j];
-              } else {
-                save = 1;
-              }
-              active[(size_t)j] = 0;
-            } else {
-              prev[(size_t)j] = rn;
-              r.steps = it + 1;
-            }
-          }
-        }
-        hflag[j] = active[(size_t)j];
-        hflag[Device::kMaxRhs + j] = save;
-        any = any || active[(size_t)j];
-      }
-      dev_.copy(dflag, hflag, sizeof(int32_t) * 2 * Device::kMaxRhs, S_MAIN);
-      dev_.copy_cols_masked(best, kw, Xloc, kw, L_.rows, kg, dflag + Device::kMaxRhs, S_MAIN);
-      if (!any) break;
-      // x += inv(A) r for the columns still active (engine dtype, added in fp64), then the whole X
-      dev_.panel_rhs(opt_.dtype, out_, L_.npad, L_, Vr, kw, kg, Xloc, kw, Xloc, kw, 1.0, dflag,
-                     dnorm + Device::kMaxRhs, S_MAIN);
-      gather_natural(Vx, Xloc);
-    }
-    // every column's returned iterate is in `best`
-    gather_natural(Vx, best);
-    dev_.copy2d(X + c0, ldx * 8, Vx, kw * 8, kg * 8, n, S_MAIN);
-    comm_.drain(dev_, S_MAIN);
-  }
-  out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return out;
-}
-
-// A^T X = B: every product is P_loc^T V_loc summed over the ranks, so B, X and R live in natural row
-// order on every rank, identical bit for bit, and so are the column norms each rank computes.
-RhsBlockResult Engine::solve_rhs_block_trans_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
-                                                  bool on_device, const GenSpec* gen, const double* host_rows,
-                                                  const void* dev_rows, int64_t ld, int max_refine, double tol) {
-  GJ_REQUIRE(solved_, "solve_rhs_block: solve() first");
-  GJ_REQUIRE(k >= 1 && ldb >= k && ldx >= k, "solve_rhs_block: k >= 1 columns, ldb >= k and ldx >= k");
-  GJ_REQUIRE(gen || host_rows || dev_rows || real_local_rows() == 0,
-             "solve_rhs_block: the matrix (generator or rows) is needed for the fp64 residual");
-  const auto t0 = std::chrono::steady_clock::now();
-  const int64_t n = L_.n;
-  const int64_t kw = std::min<int64_t>(k, Device::kMaxRhs);  // widest group = every buffer's leading dimension
-  RhsBlockResult out;
-  out.col.resize((size_t)k);
-  BufSet bufs(dev_);
-  // A's local rows in fp64, once per call
-  double* Aw = bufs.get<double>((size_t)std::max<int64_t>(L_.rows, 1) * L_.npad, false);
-  if (gen) {
-    dev_.generate(DType::F64, Aw, L_, *gen, S_MAIN);
-  } else if (dev_rows) {  // zero + identity padding, then the real rows device-to-device
-    GenSpec z;
-    z.kind = GenKind::Zero;
-    dev_.generate(DType::F64, Aw, L_, z, S_MAIN);
-    const int64_t real = real_local_rows();
-    if (real > 0) dev_.copy2d(Aw, L_.npad * 8, dev_rows, ld * 8, n * 8, real, S_MAIN);
-  } else {
-    upload_rows_into(Aw, DType::F64, host_rows, ld);
-  }
-  // ||A^T||_inf = ||A||_1: the column sums of every rank's rows, summed over the ranks
-  double* csum = bufs.get<double>((size_t)std::max<int64_t>(n, 1));
-  dev_.col_abs_sum(DType::F64, Aw, L_.npad, L_, csum, S_MAIN);
-  comm_.allreduce_sum(dev_, csum, (size_t)n, DType::F64, S_MAIN);
-  std::vector<double> hsum((size_t)n);
-  dev_.copy(hsum.data(), csum, sizeof(double) * (size_t)n, S_MAIN);
-  comm_.drain(dev_, S_MAIN);
-  double an = 0.0;
-  for (double v : hsum) an = max_keep_nan(an, v);
-
-  const size_t nat = (size_t)std::max<int64_t>(n, 1) * kw;
-  double* Vb = bufs.get<double>(nat);     // B
-  double* Vx = bufs.get<double>(nat);     // the iterate X
-  double* Vr = bufs.get<double>(nat);     // the residual R
-  double* Sp = bufs.get<double>(nat);     // a product: this rank's term, then the sum over the ranks
-  double* best = bufs.get<double>(nat);   // the best iterate
-  double* dnorm = bufs.get<double>(2 * Device::kMaxRhs);    // ||r_j|| | ||x_j||
-  int32_t* dflag = bufs.get<int32_t>(2 * Device::kMaxRhs);  // active | save-mask
-  double* hnorm = bufs.get_pinned<double>(2 * Device::kMaxRhs);
-  int32_t* hflag = bufs.get_pinned<int32_t>(2 * Device::kMaxRhs);
-  std::vector<double> hb;  // a device-resident B's columns on the host, for ||b_j|| only
-
-  // dst = C_in + sign * P^T V over all ranks, for the active columns
-  auto product = [&](DType dt, const void* P, const double* V, int64_t kg, const double* C_in, double* dst,
-                     double sign, const int32_t* act, double* colmax) {
-    dev_.panel_rhs_t(dt, P, L_.npad, L_, V, kw, kg, Sp, kw, act, S_MAIN);
-    comm_.allreduce_sum(dev_, Sp, nat, DType::F64, S_MAIN);
-    dev_.axpy_cols_masked(dst, kw, C_in, kw, Sp, kw, sign, n, kg, act, colmax, S_MAIN);
-  };
-
-  for (int64_t c0 = 0; c0 < k; c0 += kw) {
-    const int64_t kg = std::min<int64_t>(kw, k - c0);
-    if (kg < kw) dev_.memset0(Sp, sizeof(double) * nat, S_MAIN);  // the columns past kg enter the sum as 0
-    dev_.copy2d(Vb, kw * 8, B + c0, ldb * 8, kg * 8, n, S_MAIN);
-    std::vector<double> bn((size_t)kg, 0.0);
-    const double* bh = B + c0;
-    int64_t ldh = ldb;
-    if (on_device) {
-      hb.resize((size_t)n * kw);
-      dev_.copy(hb.data(), Vb, sizeof(double) * (size_t)n * kw, S_MAIN);
-      dev_.sync_stream(S_MAIN);
-      bh = hb.data();
-      ldh = kw;
-    }
-    for (int64_t i = 0; i < n; ++i)
-      for (int64_t j = 0; j < kg; ++j) bn[(size_t)j] = std::max(bn[(size_t)j], std::fabs(bh[i * ldh + j]));
-    for (double& v : bn)
-      if (v == 0) v = 1;
-
-    // x_0 = inv(A)^T b in the engine dtype, every column active
-    dev_.host_access(hflag, sizeof(int32_t) * 2 * Device::kMaxRhs, true);
-    for (int64_t j = 0; j < Device::kMaxRhs; ++j) hflag[j] = j < kg ? 1 : 0;
-    dev_.copy(dflag, hflag, sizeof(int32_t) * Device::kMaxRhs, S_MAIN);
-    product(opt_.dtype, out_, Vb, kg, nullptr, Vx, 1.0, nullptr, dnorm + Device::kMaxRhs);
-
-    std::vector<int> active((size_t)kg, 1);
-    std::vector<double> best_rn((size_t)kg, 1e300), prev((size_t)kg, 1e300);
-    std::vector<RhsResult> bestr((size_t)kg);
-    RhsResult* rr = out.col.data() + c0;
-    for (int it = 0;; ++it) {
-      // r = b - A^T x in fp64
-      product(DType::F64, Aw, Vx, kg, Vb, Vr, -1.0, dflag, dnorm);
-      dev_.copy(hnorm, dnorm, sizeof(double) * 2 * Device::kMaxRhs, S_MAIN);
-      comm_.drain(dev_, S_MAIN);
-      dev_.host_access(hnorm, sizeof(double) * 2 * Device::kMaxRhs, false);
-      out.sweeps = std::max(out.sweeps, it + 1);
-      // the per-column decision of solve_rhs
-      dev_.host_access(hflag, sizeof(int32_t) * 2 * Device::kMaxRhs, true);
-      bool any = false;
-      for (int64_t j = 0; j < kg; ++j) {
-        int32_t save = 0;
-        if (active[(size_t)j]) {
-          const double rn = hnorm[j], xn = hnorm[Device::kMaxRhs + j];
-          RhsResult& r = rr[j];
-          r.history.push_back(rn / bn[(size_t)j]);
-          r.residual = rn;
-          r.backward_error = rn / (an * xn + bn[(size_t)j]);
-          if (r.backward_error <= tol) {
-            r.converged = true;
-            active[(size_t)j] = 0;
-            save = 1;
-          } else {
-            if (rn < best_rn[(size_t)j]) {
-              best_rn[(size_t)j] = rn;
-              bestr[(size_t)j] = r;
-              save = 1;
-            }
-            if (it >= max_refine || (it > 0 && rn > 0.5 * prev[(size_t)j])) {  // budget spent / not contracting
-              if (rn > best_rn[(size_t)j]) {  // the best iterate (already saved), with its own residual
-                bestr[(size_t)j].history = r.history;
-                r = bestr[(size_t)j];
-              } else {
-                save = 1;
-              }
-              active[(size_t)j] = 0;
-            } else {
-              prev[(size_t)j] = rn;
-              r.steps = it + 1;
-            }
-          }
-        }
-        hflag[j] = active[(size_t)j];
-        hflag[Device::kMaxRhs + j] = save;
-        any = any || active[(size_t)j];
-      }
-      dev_.copy(dflag, hflag, sizeof(int32_t) * 2 * Device::kMaxRhs, S_MAIN);
-      dev_.copy_cols_masked(best, kw, Vx, kw, n, kg, dflag + Device::kMaxRhs, S_MAIN);
-      if (!any) break;
-      // x += inv(A)^T r for the columns still active (engine dtype, added in fp64)
-      product(opt_.dtype, out_, Vr, kg, Vx, Vx, 1.0, dflag, dnorm + Device::kMaxRhs);
-    }
-    // every column's returned iterate is in `best`
-    dev_.copy2d(X + c0, ldx * 8, best, kw * 8, kg * 8, n, S_MAIN);
-    comm_.drain(dev_, S_MAIN);
-  }
-  out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return out;
-}
-
-// ---------------------------------------------------------------- inv(A + U V^T) from inv(A)
-UpdateResult Engine::update_inverse(const double* U, int64_t ldu, const double* V, int64_t ldv, int64_t k) {
-  return update_inverse_impl(U, ldu, V, ldv, k);
-}
-
-// (Device::copy2d takes host and device sources alike, as in solve_rhs_block_device)
-UpdateResult Engine::update_inverse_device(const double* U_dev, int64_t ldu, const double* V_dev, int64_t ldv,
-                                           int64_t k) {
-  return update_inverse_impl(U_dev, ldu, V_dev, ldv, k);
-}
-
-UpdateResult Engine::update_inverse_impl(const double* U, int64_t ldu, const double* V, int64_t ldv, int64_t k) {
-  GJ_REQUIRE(solved_, "update_inverse: solve() first");
-  GJ_REQUIRE(k >= 1 && k <= Device::kMaxRhs, "update_inverse: 1 <= k <= 64 columns (apply a larger update in pieces)");
-  GJ_REQUIRE(U && V && ldu >= k && ldv >= k, "update_inverse: U and V are n x k, ldu >= k and ldv >= k");
-  const auto t0 = std::chrono::steady_clock::now();
-  const int64_t n = L_.n, rows = L_.rows;
-  UpdateResult out;
-  out.k = k;
-  BufSet bufs(dev_);
-  const size_t nat = (size_t)std::max<int64_t>(n, 1) * k, loc = (size_t)std::max<int64_t>(rows, 1) * k;
-  double* Ud = bufs.get<double>(nat);    // U, V, Z = X^T V: natural row order, ld k
-  double* Vd = bufs.get<double>(nat);
-  double* Z = bufs.get<double>(nat);
-  double* Wl = bufs.get<double>(loc);    // this rank's rows of W = X U, then of W inv(C)
-  double* Wc = bufs.get<double>(loc);
-  double* Cd = bufs.get<double>((size_t)k * k);  // V^T X U, then inv(C)
-  dev_.copy2d(Ud, k * 8, U, ldu * 8, k * 8, n, S_MAIN);
-  dev_.copy2d(Vd, k * 8, V, ldv * 8, k * 8, n, S_MAIN);
-  dev_.panel_rhs(opt_.dtype, out_, L_.npad, L_, Ud, k, k, nullptr, k, Wl, k, 1.0, nullptr, nullptr, S_MAIN);
-  dev_.panel_rhs_t(opt_.dtype, out_, L_.npad, L_, Vd, k, k, Z, k, nullptr, S_MAIN);
-  comm_.allreduce_sum(dev_, Z, nat, DType::F64, S_MAIN);
-  // T = Z^T U = V^T X U, the same bits on every rank (Z and U are); C = I + T is formed on the host
-  dev_.gemm(DType::F64, GemmOp::Store, ALayout::KMajor, k, k, n, Z, k, Ud, k, Cd, k, S_MAIN);
-  std::vector<double> T((size_t)k * k);
-  dev_.copy(T.data(), Cd, sizeof(double) * (size_t)k * k, S_MAIN);
-  comm_.drain(dev_, S_MAIN);
-
-  // LU with partial pivoting of C in fp64; inv(C) column by column
-  double tmax = 0.0, c1 = 0.0;
-  for (double v : T) tmax = max_keep_nan(tmax, std::fabs(v));
-  const double scale = std::isfinite(tmax) ? std::max(1.0, tmax) : tmax;
-  std::vector<double> C(T);
-  for (int64_t i = 0; i < k; ++i) C[(size_t)(i * k + i)] += 1.0;
-  for (int64_t j = 0; j < k; ++j) {
-    double s = 0.0;
-    for (int64_t i = 0; i < k; ++i) s += std::fabs(C[(size_t)(i * k + j)]);
-    c1 = max_keep_nan(c1, s);
-  }
-  std::vector<int64_t> perm((size_t)k);
-  for (int64_t i = 0; i < k; ++i) perm[(size_t)i] = i;
-  bool singular = !std::isfinite(scale);
-  double minpiv = std::numeric_limits<double>::infinity();
-  for (int64_t c = 0; c < k && !singular; ++c) {
-    int64_t pr = c;
-    for (int64_t i = c + 1; i < k; ++i)
-      if (std::fabs(C[(size_t)(i * k + c)]) > std::fabs(C[(size_t)(pr * k + c)])) pr = i;
-    if (pr != c) {
-      for (int64_t j = 0; j < k; ++j) std::swap(C[(size_t)(c * k + j)], C[(size_t)(pr * k + j)]);
-      std::swap(perm[(size_t)c], perm[(size_t)pr]);
-    }
-    const double piv = C[(size_t)(c * k + c)];
-    if (!std::isfinite(piv) || std::fabs(piv) <= opt_.eps * scale) {
-      singular = true;
-      minpiv = std::isfinite(piv) ? std::min(minpiv, std::fabs(piv) / scale) : 0.0;
-      break;
-    }
-    minpiv = std::min(minpiv, std::fabs(piv) / scale);
-    for (int64_t i = c + 1; i < k; ++i) {
-      const double l = C[(size_t)(i * k + c)] / piv;
-      C[(size_t)(i * k + c)] = l;
-      for (int64_t j = c + 1; j < k; ++j) C[(size_t)(i * k + j)] -= l * C[(size_t)(c * k + j)];
-    }
-  }
-  std::vector<double> Ci((size_t)k * k, 0.0);
-  if (!singular) {
-    std::vector<double> y((size_t)k);
-    for (int64_t e = 0; e < k; ++e) {  // C x = e_e: L y = P e_e, U x = y
-      for (int64_t i = 0; i < k; ++i) {
-        double v = perm[(size_t)i] == e ? 1.0 : 0.0;
-        for (int64_t j = 0; j < i; ++j) v -= C[(size_t)(i * k + j)] * y[(size_t)j];
-        y[(size_t)i] = v;
-      }
-      for (int64_t i = k - 1; i >= 0; --i) {
-        double v = y[(size_t)i];
-        for (int64_t j = i + 1; j < k; ++j) v -= C[(size_t)(i * k + j)] * Ci[(size_t)(j * k + e)];
-        Ci[(size_t)(i * k + e)] = v / C[(size_t)(i * k + i)];
-      }
-    }
-    double ci1 = 0.0;
-    for (int64_t j = 0; j < k; ++j) {
-      double s = 0.0;
-      for (int64_t i = 0; i < k; ++i) s += std::fabs(Ci[(size_t)(i * k + j)]);
-      ci1 = max_keep_nan(ci1, s);
-    }
-    out.cond1 = c1 * ci1;
-    if (!std::isfinite(ci1)) singular = true;
-  }
-  out.min_pivot = minpiv;
-  // one outcome for all ranks, before anything is written
-  if (comm_.host_max(dev_, singular ? 1.0 : 0.0) > 0) {
-    out.status = Status::Singular;
-    out.cond1 = 0.0;
-    out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return out;
-  }
-  dev_.copy(Cd, Ci.data(), sizeof(double) * (size_t)k * k, S_MAIN);
-  if (rows > 0)
-    dev_.gemm(DType::F64, GemmOp::Store, ALayout::RowMajor, rows, k, k, Wl, k, Cd, k, Wc, k, S_MAIN);
-  dev_.rank_update(opt_.dtype, out_, L_.npad, L_, Wc, k, false, Z, k, k, -1.0, S_MAIN);
-  comm_.drain(dev_, S_MAIN);  // (Ci is read by the copy until here)
-  out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return out;
-}
-
 void SelfComm::host_allgather(Device&, const void* send, void* recv, size_t bytes) {
   if (send != recv) std::memcpy(recv, send, bytes);
 }

@@ -36,6 +36,8 @@ def _run(binary, *args):
     ("--gen", "random", "--rhs", "random", "--profile", "--json", 300, 64),
     ("-p", 5, 33, 10),            # more ranks than some block rows
     ("--dtype", "fp32", "-p", 2, 96, 12),
+    ("-p", 3, "--gen", "randshift", "--rhs", "random", "--nrhs", 5, 200, 16),             # block solve
+    ("-p", 3, "--gen", "randshift", "--rhs", "random", "--nrhs", 3, "--trans", 100, 12),  # A^T, ragged last block
 ])
 def test_asan_cli_runs(asan_bin, args):
     p = _run(asan_bin, *args)
