@@ -59,6 +59,16 @@ struct Layout {
   GJ_HD int64_t global_row(int64_t local_row) const {
     return ((local_row / m) * p + k) * m + local_row % m;
   }
+  // this rank's real local rows (global row < n): all but the padding of the last global block
+  // row, a prefix of its rows
+  GJ_HD int64_t real_rows() const {
+    int64_t r = 0;
+    for (int64_t b = 0; b < nblk; ++b) {
+      const int64_t h = n - global_block(b) * m;
+      r += h < 0 ? 0 : h < m ? h : m;
+    }
+    return r;
+  }
 };
 
 }  // namespace gj

@@ -16,6 +16,7 @@
 #include "gj/gen.hpp"
 #include "kernels.hpp"
 #include "pivot_select.hpp"
+#include "skinny.hpp"
 #include "wave_ops.hpp"
 
 namespace gj {
@@ -35,13 +36,7 @@ __device__ inline void atomic_max_nonneg(double* addr, double v) {
   atomicMax(reinterpret_cast<unsigned long long*>(addr), (unsigned long long)__double_as_longlong(v));
 }
 
-// The same order for reductions in registers: the bit pattern of a non-negative double, NaN (of
-// either sign) as the canonical quiet NaN, which lies above +Inf.  An integer maximum over these
-// keeps a NaN that fmax would drop.
-__device__ inline unsigned long long nonneg_key(double v) {
-  v = (v >= 0.0) ? fabs(v) : __longlong_as_double(0x7ff8000000000000ll);  // fabs: -0.0 -> +0.0
-  return (unsigned long long)__double_as_longlong(v);
-}
+// wave maximum of nonneg_key()s (skinny.hpp): the same order for reductions in registers
 __device__ inline unsigned long long wave_max_key(unsigned long long x) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {

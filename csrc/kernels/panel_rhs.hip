@@ -11,6 +11,7 @@
 //           NF = 1 | 2 | 4 column fragments of 16 (v_mfma_{f64,f32}_16x16x4), walks its K-slice and
 //           stores the partial product, widened to fp64, to part[slice][row][col]
 //   pass 2  Y = C_in + sign * sum_{slice} part in slice order, and the column maxima
+//           (col_epilogue_kernel with the SliceSum source, skinny.hpp)
 //
 // Where a launch has fewer row tiles than the chip needs to saturate HBM, K is split over S
 // workgroups (auto, or set_rhs_splitk).  The slices are summed by pass 2 in a fixed order and the
@@ -24,9 +25,9 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdio>
 
 #include "kernels.hpp"
+#include "skinny.hpp"
 
 namespace gj {
 namespace kern {
@@ -39,41 +40,13 @@ constexpr int kRhsTileM = 16 * kRhsMI * kRhsWaves;    // 128 rows per workgroup
 constexpr int kRhsKC = 32;                            // rows of V per LDS stage
 constexpr int kRhsMaxSplit = 64;
 
+// LDS row padding of V (elements): the 4 K lanes of a B-fragment read sit W rows apart; W * pitch =
+// 128 (mod 256) bytes in fp64 (pad 8), 64 (mod 256) bytes in fp32 (pad 4), spreads them over the banks
 template <typename T>
-struct RhsMfma;
-template <>
-struct RhsMfma<double> {
-  typedef double acc_t __attribute__((ext_vector_type(4)));
-  typedef double vec_t __attribute__((ext_vector_type(2)));
-  static constexpr int W = 2;  // elements of a 16-byte load
-  // LDS row padding: the 4 K lanes of a B-fragment read sit W rows apart; W * pitch = 128 (mod 256)
-  // bytes spreads them over the banks
-  static constexpr int kLdsPad = 8;
-  static __device__ __forceinline__ acc_t op(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int q) { return (lane >> 4) + 4 * q; }
-};
-template <>
-struct RhsMfma<float> {
-  typedef float acc_t __attribute__((ext_vector_type(4)));
-  typedef float vec_t __attribute__((ext_vector_type(4)));
-  static constexpr int W = 4;
-  static constexpr int kLdsPad = 4;  // W * pitch = 64 (mod 256) bytes
-  static __device__ __forceinline__ acc_t op(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int q) { return 4 * (lane >> 4) + q; }
-};
-
-// the order of non-negative doubles as integers, NaN (either sign) above +Inf: misc.hip nonneg_key
-__device__ __forceinline__ unsigned long long rhs_key(double v) {
-  v = (v >= 0.0) ? fabs(v) : __longlong_as_double(0x7ff8000000000000ll);
-  return (unsigned long long)__double_as_longlong(v);
-}
+constexpr int kRhsLdsPad = sizeof(T) == 8 ? 8 : 4;
 
 // Pass 1.  W = elements each lane loads per row and K step (1: element loads, any alignment;
-// RhsMfma<T>::W: one 16-byte load, rows and K-slices 16-byte aligned).  A K step covers 4 W
+// SkinnyMfma<T>::W: one 16-byte load, rows and K-slices 16-byte aligned).  A K step covers 4 W
 // columns: lane (i = lane % 16, g = lane / 16) holds P[row i][kb + g W + j], j < W, and the j-th
 // MFMA of the step multiplies the columns {kb + g W + j : g < 4} -- any assignment of K indices to
 // the 4 MFMA K lanes is a valid product as long as the B operand uses the same one.
@@ -87,10 +60,10 @@ __global__ __launch_bounds__(64 * kRhsWaves) void panel_rhs_kernel(
     const T* __restrict__ P, int64_t ldp, int64_t rows, int64_t n, int64_t m, int64_t p, int64_t rk,
     const double* __restrict__ V, int64_t ldv, int k, const int32_t* __restrict__ active,
     double* __restrict__ part, int64_t rows_pad, int64_t kchunk, unsigned long long* colmax) {
-  using MF = RhsMfma<T>;
+  using MF = SkinnyMfma<T>;
   constexpr int KW = 16 * NF;
   constexpr int NT = 64 * kRhsWaves;
-  constexpr int LDK = KW + RhsMfma<T>::kLdsPad;   // LDS row pitch (elements)
+  constexpr int LDK = KW + kRhsLdsPad<T>;         // LDS row pitch (elements)
   constexpr int VPT = kRhsKC * KW / NT;           // elements of a V chunk per thread (column fixed)
   constexpr int STEPS = kRhsKC / (4 * W);         // K steps per chunk
   static_assert(NT % KW == 0 && (kRhsKC * KW) % NT == 0 && kRhsKC % (4 * W) == 0, "chunk shape");
@@ -187,42 +160,6 @@ __global__ __launch_bounds__(64 * kRhsWaves) void panel_rhs_kernel(
         out[(int64_t)(mi * 16 + MF::row(lane, q)) * KW + nf * 16 + i] = (double)acc[mi][nf][q];
 }
 
-// Pass 2: a workgroup covers rpb rows x KW columns (thread = column tid % KW, row group tid / KW).
-template <int KW>
-__global__ __launch_bounds__(256) void panel_rhs_epilogue(
-    const double* __restrict__ part, int S, int64_t rows_pad, int64_t rows, int64_t n, int64_t m, int64_t p,
-    int64_t rk, int k, const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign,
-    const int32_t* __restrict__ active, unsigned long long* colmax, int rpb) {
-  constexpr int RG = 256 / KW;
-  const int c = threadIdx.x % KW, rs = threadIdx.x / KW;
-  const bool on = c < k && (!active || active[c] != 0);
-  const int64_t base = (int64_t)blockIdx.x * rpb;
-  const int64_t end = base + rpb < rows ? base + rpb : rows;
-  unsigned long long key = 0ull;
-  if (on)
-    for (int64_t r = base + rs; r < end; r += RG) {
-      const bool real = ((r / m) * p + rk) * m + r % m < n;
-      double y = C_in ? C_in[r * ldc + c] : 0.0;
-      if (real) {
-        double sum = 0.0;
-        for (int s = 0; s < S; ++s) sum += part[((int64_t)s * rows_pad + r) * KW + c];
-        y += sign * sum;
-        const unsigned long long kk = rhs_key(fabs(y));
-        key = kk > key ? kk : key;
-      }
-      Y[r * ldy + c] = y;
-    }
-  if (!colmax) return;
-  __shared__ unsigned long long sh[256];
-  sh[threadIdx.x] = key;
-  __syncthreads();
-  if (rs == 0 && on) {
-#pragma unroll
-    for (int q = 1; q < RG; ++q) key = sh[q * KW + c] > key ? sh[q * KW + c] : key;
-    atomicMax(colmax + c, key);  // an integer maximum: the same bits in any order
-  }
-}
-
 __global__ __launch_bounds__(256) void gather_rows_natural_kernel(double* __restrict__ dst, int64_t ldd,
                                                                   const double* __restrict__ src, int64_t lds,
                                                                   int64_t n, int64_t m, int64_t p, int64_t per,
@@ -245,20 +182,6 @@ __global__ __launch_bounds__(256) void copy_cols_masked_kernel(double* __restric
 }
 
 int g_rhs_splitk = 0;  // set_rhs_splitk
-thread_local char g_rhs_name[48] = "";
-
-int num_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      ncu = v;
-    else
-      ncu = 256;
-  }
-  return ncu;
-}
 
 struct RhsPlan {
   int64_t tiles, rows_pad, kchunk;
@@ -288,21 +211,11 @@ void launch_rhs(const void* P, int64_t ldp, const Layout& L, const double* V, in
                 hipStream_t s) {
   const dim3 grid((unsigned)pl.tiles, (unsigned)pl.S), block(64 * kRhsWaves);
   if (vec)
-    hipLaunchKernelGGL((panel_rhs_kernel<T, NF, RhsMfma<T>::W>), grid, block, 0, s, static_cast<const T*>(P), ldp,
+    hipLaunchKernelGGL((panel_rhs_kernel<T, NF, SkinnyMfma<T>::W>), grid, block, 0, s, static_cast<const T*>(P), ldp,
                        L.rows, L.n, L.m, L.p, L.k, V, ldv, k, active, part, pl.rows_pad, pl.kchunk, colmax);
   else
     hipLaunchKernelGGL((panel_rhs_kernel<T, NF, 1>), grid, block, 0, s, static_cast<const T*>(P), ldp, L.rows,
                        L.n, L.m, L.p, L.k, V, ldv, k, active, part, pl.rows_pad, pl.kchunk, colmax);
-}
-
-template <int KW>
-void launch_rhs_epilogue(const double* part, const RhsPlan& pl, const Layout& L, int k, const double* C_in,
-                         int64_t ldc, double* Y, int64_t ldy, double sign, const int32_t* active,
-                         unsigned long long* colmax, hipStream_t s) {
-  const int rpb = 4 * (256 / KW);
-  const unsigned grid = (unsigned)std::max<int64_t>((L.rows + rpb - 1) / rpb, 1);
-  hipLaunchKernelGGL((panel_rhs_epilogue<KW>), dim3(grid), dim3(256), 0, s, part, pl.S, pl.rows_pad, L.rows, L.n,
-                     L.m, L.p, L.k, k, C_in, ldc, Y, ldy, sign, active, colmax, rpb);
 }
 
 }  // namespace
@@ -312,35 +225,26 @@ const char* last_rhs_kernel() { return g_last_rhs_kernel; }
 
 size_t panel_rhs_scratch_bytes(const Layout& L, int64_t k) {
   const RhsPlan pl = rhs_plan(L);
-  const int kw = k <= 16 ? 16 : k <= 32 ? 32 : 64;
-  return sizeof(double) * (size_t)pl.S * (size_t)pl.rows_pad * kw;
+  return sizeof(double) * (size_t)pl.S * (size_t)pl.rows_pad * padded_kw(k);
 }
 
 void panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
                const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign, const int32_t* active,
                double* colmax, void* scratch, hipStream_t s) {
   const RhsPlan pl = rhs_plan(L);
-  const int nf = k <= 16 ? 1 : k <= 32 ? 2 : 4;
   // 16-byte loads of P need 16-byte aligned rows; the K-slices start on multiples of 16 columns
-  const size_t es = dtype_size(dt);
-  const bool vec = reinterpret_cast<uintptr_t>(P) % 16 == 0 && ((size_t)ldp * es) % 16 == 0;
+  const bool vec = rows_16B_aligned(P, ldp, dtype_size(dt));
   double* part = static_cast<double*>(scratch);
   unsigned long long* cm = reinterpret_cast<unsigned long long*>(colmax);
-  std::snprintf(g_rhs_name, sizeof(g_rhs_name), "rhs%d:%s:%s:s%d", 16 * nf, dt == DType::F64 ? "f64" : "f32",
-                vec ? "vec" : "scalar", pl.S);
-  g_last_rhs_kernel = g_rhs_name;
-#define GJ_RHS_LAUNCH(T)                                                                  \
-  do {                                                                                    \
-    if (nf == 1) launch_rhs<T, 1>(P, ldp, L, V, ldv, (int)k, active, part, pl, cm, vec, s); \
-    else if (nf == 2) launch_rhs<T, 2>(P, ldp, L, V, ldv, (int)k, active, part, pl, cm, vec, s); \
-    else launch_rhs<T, 4>(P, ldp, L, V, ldv, (int)k, active, part, pl, cm, vec, s);       \
-  } while (0)
-  if (dt == DType::F64) GJ_RHS_LAUNCH(double);
-  else GJ_RHS_LAUNCH(float);
-#undef GJ_RHS_LAUNCH
-  if (nf == 1) launch_rhs_epilogue<16>(part, pl, L, (int)k, C_in, ldc, Y, ldy, sign, active, cm, s);
-  else if (nf == 2) launch_rhs_epilogue<32>(part, pl, L, (int)k, C_in, ldc, Y, ldy, sign, active, cm, s);
-  else launch_rhs_epilogue<64>(part, pl, L, (int)k, C_in, ldc, Y, ldy, sign, active, cm, s);
+  set_probe_name<struct RhsProbe>(g_last_rhs_kernel, "rhs%d:%s:%s:s%d", padded_kw(k),
+                                  dt == DType::F64 ? "f64" : "f32", vec ? "vec" : "scalar", pl.S);
+  with_kw(k, [&](auto KW) {
+    constexpr int NF = KW / 16;
+    if (dt == DType::F64) launch_rhs<double, NF>(P, ldp, L, V, ldv, (int)k, active, part, pl, cm, vec, s);
+    else launch_rhs<float, NF>(P, ldp, L, V, ldv, (int)k, active, part, pl, cm, vec, s);
+    const SliceSum<KW> sum{part, pl.S, pl.rows_pad, L.n, L.m, L.p, L.k};
+    launch_col_epilogue<KW>(sum, C_in, ldc, Y, ldy, sign, L.rows, (int)k, active, cm, s);
+  });
 }
 
 void gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L, int64_t k,

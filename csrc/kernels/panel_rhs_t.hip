@@ -28,9 +28,9 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdio>
 
 #include "kernels.hpp"
+#include "skinny.hpp"
 
 namespace gj {
 namespace kern {
@@ -41,41 +41,15 @@ constexpr int kRtWaves = 4;       // waves per workgroup, each on its own column
 constexpr int kRtKC = 32;         // local rows per LDS stage of V
 constexpr int kRtMaxSplit = 64;
 
+// LDS row padding of V (elements) at column width kw: the 4 K lanes of a B-fragment read sit on
+// consecutive rows.  fp64: pitch = 16 (mod 32) elements, 128 (mod 256) bytes apart; fp32: pitch = 16
+// (mod 64) elements, 64 (mod 256) bytes apart.
 template <typename T>
-struct RtMfma;
-template <>
-struct RtMfma<double> {
-  typedef double acc_t __attribute__((ext_vector_type(4)));
-  typedef double vec_t __attribute__((ext_vector_type(2)));
-  static constexpr int W = 2;  // elements of a 16-byte load
-  // LDS row pitch = 16 (mod 32) elements: the 4 K lanes of a B-fragment read sit on consecutive
-  // rows, 128 (mod 256) bytes apart
-  static constexpr int pad(int kw) { return kw == 16 ? 0 : 16; }
-  static __device__ __forceinline__ acc_t op(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int q) { return (lane >> 4) + 4 * q; }
-};
-template <>
-struct RtMfma<float> {
-  typedef float acc_t __attribute__((ext_vector_type(4)));
-  typedef float vec_t __attribute__((ext_vector_type(4)));
-  static constexpr int W = 4;
-  // pitch = 16 (mod 64) elements: consecutive rows 64 (mod 256) bytes apart
-  static constexpr int pad(int kw) { return kw == 16 ? 0 : kw == 32 ? 48 : 16; }
-  static __device__ __forceinline__ acc_t op(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int row(int lane, int q) { return 4 * (lane >> 4) + q; }
-};
-
-// the order of non-negative doubles as integers, NaN (either sign) above +Inf: misc.hip nonneg_key
-__device__ __forceinline__ unsigned long long rt_key(double v) {
-  v = (v >= 0.0) ? fabs(v) : __longlong_as_double(0x7ff8000000000000ll);
-  return (unsigned long long)__double_as_longlong(v);
+constexpr int rt_lds_pad(int kw) {
+  return kw == 16 ? 0 : (sizeof(T) == 4 && kw == 32) ? 48 : 16;
 }
 
-// Pass 1.  W = elements each lane loads per row (1: element loads, any alignment; RtMfma<T>::W: one
+// Pass 1.  W = elements each lane loads per row (1: element loads, any alignment; SkinnyMfma<T>::W: one
 // 16-byte load, rows 16-byte aligned).  A K step covers 4 local rows: lane (i = lane % 16,
 // g = lane / 16) holds P[row + g][c0 + i W + j], j < W, and the j-th MFMA of the step produces the
 // output rows {c0 + i W + j : i < 16} -- W interleaved column fragments from one load.
@@ -89,10 +63,10 @@ __global__ __launch_bounds__(64 * kRtWaves) void panel_rhs_t_kernel(
     const T* __restrict__ P, int64_t ldp, int64_t real, int64_t n, uint32_t m, int64_t p, int64_t rk,
     const double* __restrict__ V, int64_t ldv, int k, const int32_t* __restrict__ active,
     double* __restrict__ part, int64_t cols_pad, int64_t rchunk) {
-  using MF = RtMfma<T>;
+  using MF = SkinnyMfma<T>;
   constexpr int KW = 16 * NF;
   constexpr int NT = 64 * kRtWaves;
-  constexpr int LDK = KW + MF::pad(KW);      // LDS row pitch (elements)
+  constexpr int LDK = KW + rt_lds_pad<T>(KW);  // LDS row pitch (elements)
   constexpr int VPT = kRtKC * KW / NT;       // elements of a V chunk per thread (column fixed)
   constexpr int STEPS = kRtKC / 4;           // K steps per chunk
   static_assert(NT % KW == 0 && (kRtKC * KW) % NT == 0 && kRtKC % 4 == 0, "chunk shape");
@@ -200,38 +174,6 @@ __global__ void axpy_cols_init_kernel(unsigned long long* colmax, int k, const i
   if (j < k && (!active || active[j] != 0)) colmax[j] = 0ull;
 }
 
-// Y = C_in + sign S on the active columns, and their maxima.  A workgroup covers rpb rows x KW columns
-// (thread = column tid % KW, row group tid / KW).
-template <int KW>
-__global__ __launch_bounds__(256) void axpy_cols_masked_kernel(double* Y, int64_t ldy, const double* C_in,
-                                                               int64_t ldc, const double* __restrict__ S,
-                                                               int64_t lds, double sign, int64_t rows, int k,
-                                                               const int32_t* __restrict__ active,
-                                                               unsigned long long* colmax, int rpb) {
-  constexpr int RG = 256 / KW;
-  const int c = threadIdx.x % KW, rs = threadIdx.x / KW;
-  const bool on = c < k && (!active || active[c] != 0);
-  const int64_t base = (int64_t)blockIdx.x * rpb;
-  const int64_t end = base + rpb < rows ? base + rpb : rows;
-  unsigned long long key = 0ull;
-  if (on)
-    for (int64_t r = base + rs; r < end; r += RG) {
-      const double y = (C_in ? C_in[r * ldc + c] : 0.0) + sign * S[r * lds + c];
-      Y[r * ldy + c] = y;
-      const unsigned long long kk = rt_key(fabs(y));
-      key = kk > key ? kk : key;
-    }
-  if (!colmax) return;
-  __shared__ unsigned long long sh[256];
-  sh[threadIdx.x] = key;
-  __syncthreads();
-  if (rs == 0 && on) {
-#pragma unroll
-    for (int q = 1; q < RG; ++q) key = sh[q * KW + c] > key ? sh[q * KW + c] : key;
-    atomicMax(colmax + c, key);  // an integer maximum: the same bits in any order
-  }
-}
-
 // out[c] = sum over the real local rows of |X[r][c]|: a workgroup covers 64 columns, its 4 row
 // groups walk the rows 4 apart and are summed in a fixed order.
 template <typename T>
@@ -249,27 +191,6 @@ __global__ __launch_bounds__(256) void col_abs_sum_kernel(const T* __restrict__ 
 }
 
 int g_rt_split = 0;  // set_rhs_t_split
-thread_local char g_rt_name[48] = "";
-
-int rt_num_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      ncu = v;
-    else
-      ncu = 256;
-  }
-  return ncu;
-}
-
-// this rank's real local rows: all but the padding of the last global block row
-int64_t real_rows(const Layout& L) {
-  int64_t r = 0;
-  for (int64_t b = 0; b < L.nblk; ++b) r += std::max<int64_t>(0, std::min<int64_t>(L.m, L.n - L.global_block(b) * L.m));
-  return r;
-}
 
 struct RtPlan {
   int64_t tiles, cols_pad, rchunk, real;
@@ -279,18 +200,17 @@ struct RtPlan {
 
 RtPlan rt_plan(DType dt, const void* P, int64_t ldp, const Layout& L) {
   RtPlan pl;
-  const size_t es = dtype_size(dt);
   // 16-byte loads of P need 16-byte aligned rows; a lane's columns start on a multiple of W
-  pl.vec = reinterpret_cast<uintptr_t>(P) % 16 == 0 && ((size_t)ldp * es) % 16 == 0;
-  pl.W = pl.vec ? (int)(16 / es) : 1;
+  pl.vec = rows_16B_aligned(P, ldp, dtype_size(dt));
+  pl.W = pl.vec ? (int)(16 / dtype_size(dt)) : 1;
   const int64_t tw = 16 * pl.W * kRtWaves;
   pl.tiles = std::max<int64_t>((L.n + tw - 1) / tw, 1);
   pl.cols_pad = pl.tiles * tw;
-  pl.real = real_rows(L);
+  pl.real = L.real_rows();
   int64_t S = g_rt_split;
   if (S <= 0) {
     // memory-bound: about two workgroups per CU keep HBM busy; a slice of at least 128 rows
-    S = (2 * (int64_t)rt_num_cus() + pl.tiles - 1) / pl.tiles;
+    S = (2 * (int64_t)num_cus() + pl.tiles - 1) / pl.tiles;
     S = std::min<int64_t>(S, std::max<int64_t>(pl.real / 128, 1));
   }
   S = std::max<int64_t>(1, std::min<int64_t>(S, kRtMaxSplit));
@@ -305,7 +225,7 @@ void launch_rt(const void* P, int64_t ldp, const Layout& L, const double* V, int
                const int32_t* active, double* part, const RtPlan& pl, hipStream_t s) {
   const dim3 grid((unsigned)pl.tiles, (unsigned)pl.S), block(64 * kRtWaves);
   if (pl.vec)
-    hipLaunchKernelGGL((panel_rhs_t_kernel<T, NF, RtMfma<T>::W>), grid, block, 0, s, static_cast<const T*>(P), ldp,
+    hipLaunchKernelGGL((panel_rhs_t_kernel<T, NF, SkinnyMfma<T>::W>), grid, block, 0, s, static_cast<const T*>(P), ldp,
                        pl.real, L.n, (uint32_t)L.m, L.p, L.k, V, ldv, k, active, part, pl.cols_pad, pl.rchunk);
   else
     hipLaunchKernelGGL((panel_rhs_t_kernel<T, NF, 1>), grid, block, 0, s, static_cast<const T*>(P), ldp, pl.real,
@@ -327,54 +247,39 @@ const char* last_rhs_t_kernel() { return g_last_rhs_t_kernel; }
 
 size_t panel_rhs_t_scratch_bytes(DType dt, const void* P, int64_t ldp, const Layout& L, int64_t k) {
   const RtPlan pl = rt_plan(dt, P, ldp, L);
-  const int kw = k <= 16 ? 16 : k <= 32 ? 32 : 64;
-  return sizeof(double) * (size_t)pl.S * (size_t)pl.cols_pad * kw;
+  return sizeof(double) * (size_t)pl.S * (size_t)pl.cols_pad * padded_kw(k);
 }
 
 void panel_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
                  double* S, int64_t lds, const int32_t* active, void* scratch, hipStream_t s) {
   if (L.n <= 0) return;
   const RtPlan pl = rt_plan(dt, P, ldp, L);
-  const int nf = k <= 16 ? 1 : k <= 32 ? 2 : 4;
   double* part = static_cast<double*>(scratch);
-  std::snprintf(g_rt_name, sizeof(g_rt_name), "rhst%d:%s:%s:s%d", 16 * nf, dt == DType::F64 ? "f64" : "f32",
-                pl.vec ? "vec" : "scalar", pl.S);
-  g_last_rhs_t_kernel = g_rt_name;
-#define GJ_RT_LAUNCH(T)                                                            \
-  do {                                                                             \
-    if (nf == 1) launch_rt<T, 1>(P, ldp, L, V, ldv, (int)k, active, part, pl, s);   \
-    else if (nf == 2) launch_rt<T, 2>(P, ldp, L, V, ldv, (int)k, active, part, pl, s); \
-    else launch_rt<T, 4>(P, ldp, L, V, ldv, (int)k, active, part, pl, s);           \
-  } while (0)
-  if (dt == DType::F64) GJ_RT_LAUNCH(double);
-  else GJ_RT_LAUNCH(float);
-#undef GJ_RT_LAUNCH
-  if (nf == 1) launch_rt_reduce<16>(part, pl, L, (int)k, S, lds, active, s);
-  else if (nf == 2) launch_rt_reduce<32>(part, pl, L, (int)k, S, lds, active, s);
-  else launch_rt_reduce<64>(part, pl, L, (int)k, S, lds, active, s);
+  set_probe_name<struct RhsTProbe>(g_last_rhs_t_kernel, "rhst%d:%s:%s:s%d", padded_kw(k),
+                                   dt == DType::F64 ? "f64" : "f32", pl.vec ? "vec" : "scalar", pl.S);
+  with_kw(k, [&](auto KW) {
+    constexpr int NF = KW / 16;
+    if (dt == DType::F64) launch_rt<double, NF>(P, ldp, L, V, ldv, (int)k, active, part, pl, s);
+    else launch_rt<float, NF>(P, ldp, L, V, ldv, (int)k, active, part, pl, s);
+    launch_rt_reduce<KW>(part, pl, L, (int)k, S, lds, active, s);
+  });
 }
 
+// Y = C_in + sign S on the active columns, and their maxima
 void axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S, int64_t lds,
                       double sign, int64_t rows, int64_t k, const int32_t* active, double* colmax, hipStream_t s) {
   unsigned long long* cm = reinterpret_cast<unsigned long long*>(colmax);
   if (cm) hipLaunchKernelGGL(axpy_cols_init_kernel, dim3(1), dim3(64), 0, s, cm, (int)k, active);
   if (rows <= 0) return;
-#define GJ_AXPY_LAUNCH(KW)                                                                                    \
-  do {                                                                                                        \
-    const int rpb = 4 * (256 / KW);                                                                           \
-    hipLaunchKernelGGL((axpy_cols_masked_kernel<KW>), dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, s, Y, \
-                       ldy, C_in, ldc, S, lds, sign, rows, (int)k, active, cm, rpb);                           \
-  } while (0)
-  if (k <= 16) GJ_AXPY_LAUNCH(16);
-  else if (k <= 32) GJ_AXPY_LAUNCH(32);
-  else GJ_AXPY_LAUNCH(64);
-#undef GJ_AXPY_LAUNCH
+  with_kw(k, [&](auto KW) {
+    launch_col_epilogue<KW>(DenseTerm{S, lds}, C_in, ldc, Y, ldy, sign, rows, (int)k, active, cm, s);
+  });
 }
 
 void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, hipStream_t s) {
   if (L.n <= 0) return;
   const unsigned grid = (unsigned)((L.n + 63) / 64);
-  const int64_t real = real_rows(L);
+  const int64_t real = L.real_rows();
   if (dt == DType::F64)
     hipLaunchKernelGGL(col_abs_sum_kernel<double>, dim3(grid), dim3(256), 0, s, static_cast<const double*>(X), ldx,
                        real, L.n, out);

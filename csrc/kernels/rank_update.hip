@@ -28,9 +28,10 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdio>
+#include <type_traits>
 
 #include "kernels.hpp"
+#include "skinny.hpp"
 
 namespace gj {
 namespace kern {
@@ -42,23 +43,6 @@ constexpr int kRkuWaves = 4;                        // waves per workgroup
 constexpr int kRkuTileM = 16 * kRkuMI * kRkuWaves;  // 64 rows per workgroup
 constexpr int kRkuNF = 4;                           // 16-column fragments per wave
 constexpr int kRkuTileN = 16 * kRkuNF;              // 64 columns per tile
-
-typedef double rku_acc_t __attribute__((ext_vector_type(4)));
-
-template <typename T, int VW>
-struct RkuVec;
-template <>
-struct RkuVec<double, 2> {
-  typedef double type __attribute__((ext_vector_type(2)));
-};
-template <>
-struct RkuVec<float, 4> {
-  typedef float type __attribute__((ext_vector_type(4)));
-};
-template <typename T>
-struct RkuVec<T, 1> {
-  typedef T type;
-};
 
 // Column (within a tile) of fragment f's B lane i: (f / VW) * 16 VW + VW i + f % VW, so a lane's VW
 // fragments of a group sit side by side.
@@ -77,7 +61,8 @@ __global__ __launch_bounds__(64 * kRkuWaves, 2) void rank_update_kernel(
   constexpr int ES = (int)sizeof(T);
   static_assert(NT % KW == 0 && (kRkuTileN * KW) % NT == 0, "Z tile shape");
   static_assert(kRkuNF % VW == 0, "fragment groups");
-  using vec_t = typename RkuVec<T, VW>::type;
+  using MF = SkinnyMfma<double>;  // both dtypes share the fp64 product
+  using vec_t = std::conditional_t<VW == 1, T, typename SkinnyMfma<T>::vec_t>;  // a lane's piece of X
   __shared__ double zs[kRkuTileN][LDK];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, g = lane >> 4;
@@ -165,11 +150,11 @@ __global__ __launch_bounds__(64 * kRkuWaves, 2) void rank_update_kernel(
     __syncthreads();
     fetch_z(ct + gridDim.y);
 
-    rku_acc_t acc[kRkuMI][kRkuNF];
+    MF::acc_t acc[kRkuMI][kRkuNF];
 #pragma unroll
     for (int mi = 0; mi < kRkuMI; ++mi)
 #pragma unroll
-      for (int f = 0; f < kRkuNF; ++f) acc[mi][f] = rku_acc_t{0, 0, 0, 0};
+      for (int f = 0; f < kRkuNF; ++f) acc[mi][f] = MF::acc_t{0, 0, 0, 0};
 #pragma unroll
     for (int st = 0; st < KS; ++st) {
       if (st < ks) {  // uniform
@@ -179,8 +164,7 @@ __global__ __launch_bounds__(64 * kRkuWaves, 2) void rank_update_kernel(
 #pragma unroll
         for (int mi = 0; mi < kRkuMI; ++mi)
 #pragma unroll
-          for (int f = 0; f < kRkuNF; ++f)
-            acc[mi][f] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi][st], b[f], acc[mi][f], 0, 0, 0);
+          for (int f = 0; f < kRkuNF; ++f) acc[mi][f] = MF::op(a[mi][st], b[f], acc[mi][f]);
       }
     }
 
@@ -214,28 +198,6 @@ __global__ __launch_bounds__(64 * kRkuWaves, 2) void rank_update_kernel(
   }
 }
 
-thread_local char g_rku_name[48] = "";
-
-int rku_num_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      ncu = v;
-    else
-      ncu = 256;
-  }
-  return ncu;
-}
-
-// this rank's real local rows: all but the padding of the last global block row (a prefix)
-int64_t rku_real_rows(const Layout& L) {
-  int64_t r = 0;
-  for (int64_t b = 0; b < L.nblk; ++b) r += std::max<int64_t>(0, std::min<int64_t>(L.m, L.n - L.global_block(b) * L.m));
-  return r;
-}
-
 template <typename T, int KS, int VW>
 void launch_rku(void* X, int64_t ldx, int64_t real, const Layout& L, const double* W, int64_t ldw, bool w_natural,
                 const double* Z, int64_t ldz, int k, double sign, hipStream_t s) {
@@ -243,7 +205,7 @@ void launch_rku(void* X, int64_t ldx, int64_t real, const Layout& L, const doubl
   const int64_t ctiles = (L.n + kRkuTileN - 1) / kRkuTileN;
   // memory-bound: about four workgroups per CU in flight; a workgroup keeps its rows of W in
   // registers over all of its column tiles
-  int64_t S = (4 * (int64_t)rku_num_cus() + rtiles - 1) / rtiles;
+  int64_t S = (4 * (int64_t)num_cus() + rtiles - 1) / rtiles;
   S = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(S, ctiles), 65535));
   const dim3 grid((unsigned)rtiles, (unsigned)S), block(64 * kRkuWaves);
   hipLaunchKernelGGL((rank_update_kernel<T, KS, VW>), grid, block, 0, s, static_cast<T*>(X), ldx, real, L.n, L.m,
@@ -269,12 +231,11 @@ void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* 
   // a tile's rows are addressed from the tile's base with 32-bit byte offsets
   if (ldx < 0 || ldx > ((int64_t(1) << 31) / es - kRkuTileN) / (kRkuTileM - 1))
     throw Error(Status::BadArgs, "rank_update: leading dimension too large for 32-bit tile offsets");
-  const int64_t real = rku_real_rows(L);
+  const int64_t real = L.real_rows();
   // 16-byte pieces of X need 16-byte aligned rows; a lane's columns start on a multiple of the width
-  const bool vec = reinterpret_cast<uintptr_t>(X) % 16 == 0 && ((size_t)ldx * (size_t)es) % 16 == 0;
-  std::snprintf(g_rku_name, sizeof(g_rku_name), "rku%d:%s:%s", (int)((k + 3) / 4 * 4), dt == DType::F64 ? "f64" : "f32",
-                vec ? "vec" : "scalar");
-  g_last_rank_update_kernel = g_rku_name;
+  const bool vec = rows_16B_aligned(X, ldx, (size_t)es);
+  set_probe_name<struct RkuProbe>(g_last_rank_update_kernel, "rku%d:%s:%s", (int)((k + 3) / 4 * 4),
+                                  dt == DType::F64 ? "f64" : "f32", vec ? "vec" : "scalar");
   if (real <= 0 || L.n <= 0) return;
   if (dt == DType::F64) {
     if (vec) launch_rku_k<double, 2>(X, ldx, real, L, W, ldw, w_natural, Z, ldz, (int)k, sign, s);

@@ -180,6 +180,18 @@ static int refine_budget(const Engine& eng, int max_refine) {
   return max_refine >= 0 ? max_refine : eng.options().dtype == DType::F64 ? 2 : 10;
 }
 
+// Device-side time of a launch: `reps` back-to-back run(i), i < reps, on one stream between two
+// timing events (no host work in between; the caller has warmed up); microseconds per call.
+template <typename F>
+static double time_launches(Device& d, int stream, int reps, F&& run) {
+  const int e0 = d.create_event(true), e1 = d.create_event(true);
+  d.record(e0, stream);
+  for (int i = 0; i < reps; ++i) run(i);
+  d.record(e1, stream);
+  d.sync_stream(stream);
+  return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
+}
+
 PYBIND11_MODULE(_C, mod) {
   mod.doc() = "MI355X-native block Gauss-Jordan inversion: native engine, HIP kernels, RCCL comm";
 
@@ -205,6 +217,9 @@ PYBIND11_MODULE(_C, mod) {
     return n;
   });
   mod.def("rccl_unique_id", [] { return py::bytes(RcclComm::unique_id()); });
+  mod.def("layout_real_rows",
+          [](int64_t n, int64_t m, int64_t p, int64_t k) { return Layout::make(n, m, p, k).real_rows(); },
+          "Layout::real_rows(): rank k's local rows whose global row is < n");
   mod.def("set_block_inverse_variant", [](const std::string& v) {
     kern::set_block_inverse_variant(kern::block_inverse_variant_id(v.c_str()));
   });
@@ -425,16 +440,12 @@ PYBIND11_MODULE(_C, mod) {
              py::gil_scoped_release rel;
              const Layout L = lay(n, m, p, k);
              const DType t = parse_dtype(dt);
-             d.block_inverse(t, (const void*)Lt, ldl, (void*)inv_t, (double*)scores, (int32_t*)valid,
-                             (const int32_t*)used, L, thresh, nlive, S_SIDE);
-             const int e0 = d.create_event(true), e1 = d.create_event(true);
-             d.record(e0, S_SIDE);
-             for (int i = 0; i < reps; ++i)
+             auto run = [&](int) {
                d.block_inverse(t, (const void*)Lt, ldl, (void*)inv_t, (double*)scores, (int32_t*)valid,
                                (const int32_t*)used, L, thresh, nlive, S_SIDE);
-             d.record(e1, S_SIDE);
-             d.sync_stream(S_SIDE);
-             return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
+             };
+             run(0);
+             return time_launches(d, S_SIDE, reps, run);
            },
            py::arg("dt"), py::arg("Lt"), py::arg("ldl"), py::arg("inv_t"), py::arg("scores"), py::arg("valid"),
            py::arg("used"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"), py::arg("thresh"),
@@ -448,17 +459,12 @@ PYBIND11_MODULE(_C, mod) {
              py::gil_scoped_release rel;
              const Layout L = lay(n, m, p, k);
              const DType t = parse_dtype(dt);
-             auto run = [&] {
+             auto run = [&](int) {
                d.panel_rhs(t, (const void*)P, ldp, L, (const double*)V, ldv, ncols, nullptr, 0, (double*)Y, ldy, 1.0,
                            nullptr, (double*)colmax, S_MAIN);
              };
-             run();
-             const int e0 = d.create_event(true), e1 = d.create_event(true);
-             d.record(e0, S_MAIN);
-             for (int i = 0; i < reps; ++i) run();
-             d.record(e1, S_MAIN);
-             d.sync_stream(S_MAIN);
-             return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
+             run(0);
+             return time_launches(d, S_MAIN, reps, run);
            })
       // The same timing of panel_rhs_t (S = P^T V, every column active) and of the K-major GEMM it is
       // measured against (C = At^T B with At = P: M = n, K = the rows of P).
@@ -468,17 +474,12 @@ PYBIND11_MODULE(_C, mod) {
              py::gil_scoped_release rel;
              const Layout L = lay(n, m, p, k);
              const DType t = parse_dtype(dt);
-             auto run = [&] {
+             auto run = [&](int) {
                d.panel_rhs_t(t, (const void*)P, ldp, L, (const double*)V, ldv, ncols, (double*)S, lds, nullptr,
                              S_MAIN);
              };
-             run();
-             const int e0 = d.create_event(true), e1 = d.create_event(true);
-             d.record(e0, S_MAIN);
-             for (int i = 0; i < reps; ++i) run();
-             d.record(e1, S_MAIN);
-             d.sync_stream(S_MAIN);
-             return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
+             run(0);
+             return time_launches(d, S_MAIN, reps, run);
            })
       // The same timing of rank_update (X -= / += W Z^T in turn, so that X stays bounded), W in local order
       .def("time_rank_update",
@@ -487,52 +488,37 @@ PYBIND11_MODULE(_C, mod) {
              py::gil_scoped_release rel;
              const Layout L = lay(n, m, p, k);
              const DType t = parse_dtype(dt);
-             auto run = [&](double sign) {
-               d.rank_update(t, (void*)X, ldx, L, (const double*)W, ldw, false, (const double*)Z, ldz, ncols, sign,
-                             S_MAIN);
+             auto run = [&](int i) {
+               d.rank_update(t, (void*)X, ldx, L, (const double*)W, ldw, false, (const double*)Z, ldz, ncols,
+                             i % 2 ? 1.0 : -1.0, S_MAIN);
              };
-             run(-1.0);
-             run(1.0);
-             const int e0 = d.create_event(true), e1 = d.create_event(true);
-             d.record(e0, S_MAIN);
-             for (int i = 0; i < reps; ++i) run(i % 2 ? 1.0 : -1.0);
-             d.record(e1, S_MAIN);
-             d.sync_stream(S_MAIN);
-             return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
+             run(0);
+             run(1);
+             return time_launches(d, S_MAIN, reps, run);
            })
       .def("time_gemm_store_kmajor",
            [](Device& d, const std::string& dt, int64_t M, int64_t N, int64_t K, U A, int64_t lda, U B, int64_t ldb,
               U C, int64_t ldc, int reps) {
              py::gil_scoped_release rel;
              const DType t = parse_dtype(dt);
-             auto run = [&] {
+             auto run = [&](int) {
                d.gemm(t, GemmOp::Store, ALayout::KMajor, M, N, K, (const void*)A, lda, (const void*)B, ldb, (void*)C,
                       ldc, S_MAIN);
              };
-             run();
-             const int e0 = d.create_event(true), e1 = d.create_event(true);
-             d.record(e0, S_MAIN);
-             for (int i = 0; i < reps; ++i) run();
-             d.record(e1, S_MAIN);
-             d.sync_stream(S_MAIN);
-             return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
+             run(0);
+             return time_launches(d, S_MAIN, reps, run);
            })
       .def("time_gemm_store",
            [](Device& d, const std::string& dt, int64_t M, int64_t N, int64_t K, U A, int64_t lda, U B, int64_t ldb,
               U C, int64_t ldc, int reps) {
              py::gil_scoped_release rel;
              const DType t = parse_dtype(dt);
-             auto run = [&] {
+             auto run = [&](int) {
                d.gemm(t, GemmOp::Store, ALayout::RowMajor, M, N, K, (const void*)A, lda, (const void*)B, ldb, (void*)C,
                       ldc, S_MAIN);
              };
-             run();
-             const int e0 = d.create_event(true), e1 = d.create_event(true);
-             d.record(e0, S_MAIN);
-             for (int i = 0; i < reps; ++i) run();
-             d.record(e1, S_MAIN);
-             d.sync_stream(S_MAIN);
-             return 1e3 * d.event_ms(e0, e1) / std::max(reps, 1);
+             run(0);
+             return time_launches(d, S_MAIN, reps, run);
            })
       .def("permute_blocks",
            [](Device& d, const std::string& dt, U dst, int64_t ldd, U X, int64_t ldx, int64_t nblk,

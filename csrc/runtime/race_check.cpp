@@ -774,9 +774,7 @@ void RaceCheckDevice::panel_rhs_t(DType dt, const void* P, int64_t ldp, const La
                                   int64_t ldv, int64_t k, double* S, int64_t lds, const int32_t* active, int s) {
   std::vector<Acc> a;
   if (k >= 1 && k <= kMaxRhs) {  // (the inner device refuses any other k before it touches memory)
-    int64_t real = 0;  // the real local rows are a prefix: only the last global block row is short
-    for (int64_t b = 0; b < L.nblk; ++b)
-      real += std::max<int64_t>(0, std::min<int64_t>(L.m, L.n - L.global_block(b) * L.m));
+    const int64_t real = L.real_rows();  // a prefix: only the last global block row is short
     a.push_back(R(rect(P, ldp, L.n, real, (int64_t)dtype_size(dt)), "P"));
     for (int64_t b = 0; b < L.nblk; ++b) {  // V: the row blocks this rank owns
       const int64_t g0 = L.global_block(b) * L.m, h = std::min<int64_t>(L.m, L.n - g0);
@@ -803,9 +801,7 @@ void RaceCheckDevice::axpy_cols_masked(double* Y, int64_t ldy, const double* C_i
   inner_->axpy_cols_masked(Y, ldy, C_in, ldc, S, lds, sign, rows, k, active, colmax, s);
 }
 void RaceCheckDevice::col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) {
-  int64_t real = 0;
-  for (int64_t b = 0; b < L.nblk; ++b)
-    real += std::max<int64_t>(0, std::min<int64_t>(L.m, L.n - L.global_block(b) * L.m));
+  const int64_t real = L.real_rows();
   check(s, "col_abs_sum", {R(rect(X, ldx, L.n, real, (int64_t)dtype_size(dt)), "X"), W(span(out, 8 * L.n), "out")});
   inner_->col_abs_sum(dt, X, ldx, L, out, s);
 }
@@ -813,9 +809,7 @@ void RaceCheckDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& 
                                   bool w_natural, const double* Z, int64_t ldz, int64_t k, double sign, int s) {
   std::vector<Acc> a;
   if (k >= 1 && k <= kMaxRhs) {  // (the inner device refuses any other k before it touches memory)
-    int64_t real = 0;  // the real local rows are a prefix: only the last global block row is short
-    for (int64_t b = 0; b < L.nblk; ++b)
-      real += std::max<int64_t>(0, std::min<int64_t>(L.m, L.n - L.global_block(b) * L.m));
+    const int64_t real = L.real_rows();  // a prefix: only the last global block row is short
     if (w_natural) {  // W: the row blocks this rank owns
       for (int64_t b = 0; b < L.nblk; ++b) {
         const int64_t g0 = L.global_block(b) * L.m, h = std::min<int64_t>(L.m, L.n - g0);

@@ -361,11 +361,7 @@ Engine::Policy Engine::policy() const {
   return p;
 }
 
-int64_t Engine::real_local_rows() const {
-  if (L_.nblk == 0) return 0;
-  const int64_t last_global_block = L_.global_block(L_.nblk - 1);
-  return L_.rows - (last_global_block == L_.Nr - 1 ? (L_.m - L_.l_h) : 0);
-}
+int64_t Engine::real_local_rows() const { return L_.real_rows(); }
 
 
 int Engine::alloc_buffers(std::string& why) {

@@ -38,3 +38,21 @@ def test_global_rows_partition():
             for i, gi in enumerate(g):
                 assert L.global_row(i) == gi
                 assert (gi // m) % p == k  # block row I lives on rank I mod p
+
+
+def test_real_rows_matches_brute_force():
+    # n a multiple of m, a short last block row on rank 0 and on another rank, ranks that own no
+    # block (p > Nr), m > n
+    from mpi_jordan_crazy_acceleration_amd import load_native
+
+    C = load_native()
+    for n, m, p in itertools.product([1, 7, 64, 65, 100], [4, 16, 64], [1, 2, 3, 5]):
+        for k in range(p):
+            L = Layout(n, m, p, k)
+            brute = sum(1 for i in range(L.nblk * m) if L.global_row(i) < n)
+            assert C.layout_real_rows(n, m, p, k) == brute, (n, m, p, k)
+    for n, m, p in [(64, 16, 1), (65, 16, 1), (7, 64, 1), (100, 16, 3), (65, 4, 5), (7, 4, 5)]:
+        comm = C.self_comm() if p == 1 else C.shadow_comm(p, 50.0, 20.0, 16)
+        lay = C.Engine(C.host_device(1), comm, n, m, "fp64").layout
+        assert (lay["p"], lay["k"]) == (p, 0)
+        assert lay["real_rows"] == C.layout_real_rows(n, m, p, 0) == len(global_rows(n, m, p, 0))
