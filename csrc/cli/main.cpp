@@ -41,6 +41,9 @@
 //                        --rhs is given
 //   --refine K           at most K refinement steps of x with the residual in fp64 (default: 10 for
 //                        fp32 solves, 2 for fp64; Engine::solve_rhs)
+//   --det                keep the pivot blocks' inverses and print "slogdet: <sign> <log|det|>" after
+//                        the residual line (Engine::slogdet; of A + U V^T after an update); --json
+//                        gains "slogdet": [sign, logabsdet]
 //   --json               machine-readable report on stderr
 //   --bcast auto|ring|direct  pivot-row broadcast algorithm at p > 2 (sets GJ_BCAST; auto = timed
 //                        against each other at startup, Comm::tune_bcast)
@@ -123,17 +126,27 @@ static void json_report(const RunConfig& cfg, const RunReport& rep) {
       });
     }
   }
+  std::string det;
+  if (rep.det_computed) {  // JSON has no NaN or Infinity: null
+    auto num = [](double v, const char* fmt) {
+      char b[64];
+      if (!std::isfinite(v)) return std::string("null");
+      std::snprintf(b, sizeof b, fmt, v);
+      return std::string(b);
+    };
+    det = ", \"slogdet\": [" + num(rep.det.sign, "%.1f") + ", " + num(rep.det.logabsdet, "%.15e") + "]";
+  }
   std::fprintf(stderr,
                "{\"n\": %lld, \"m\": %lld, \"ranks\": %d, \"device\": \"%s\", \"comm\": \"%s\", "
                "\"dtype\": \"%s\", \"status\": %d, \"glob_time\": %.6f, \"best_time\": %.6f, "
                "\"gflops_nominal\": %.3f, \"residual\": %.6e, \"residual_computed\": %s, "
-               "\"residual_fp64\": %s, \"host_wait_ms\": %.3f, \"offdiag_pivots\": %lld, \"pivot_fallbacks\": %lld%s%s}\n",
+               "\"residual_fp64\": %s, \"host_wait_ms\": %.3f, \"offdiag_pivots\": %lld, \"pivot_fallbacks\": %lld%s%s%s}\n",
                (long long)cfg.n, (long long)cfg.m, cfg.ranks, rep.device_desc.c_str(),
                rep.comm_desc.c_str(), dtype_name(cfg.solve.dtype), (int)rep.status, rep.glob_time,
                rep.best_time, rep.gflops_nominal, rep.residual,
                rep.residual_computed ? "true" : "false", rep.residual_fp64 ? "true" : "false",
                rep.stats.host_wait_ms,
-               (long long)rep.stats.offdiag_pivots, (long long)rep.stats.pivot_fallbacks, phases.c_str(), rhs.c_str());
+               (long long)rep.stats.offdiag_pivots, (long long)rep.stats.pivot_fallbacks, phases.c_str(), rhs.c_str(), det.c_str());
 }
 
 int main(int argc, char* argv[]) {
@@ -206,6 +219,7 @@ int main(int argc, char* argv[]) {
       else if (a == "--out-x") x_file = val("--out-x");
       else if (a == "--refine") cfg.refine = std::atoi(val("--refine"));
       else if (a == "--json") json = true;
+      else if (a == "--det") cfg.solve.track_det = true;
       else if (a == "--bcast") {
         const std::string b = val("--bcast");
         if (b != "auto" && b != "ring" && b != "direct") return usage(argv[0]);
@@ -280,6 +294,10 @@ int main(int argc, char* argv[]) {
     std::printf("residual: %e\n", rep.residual);
   else if (cfg.residual == ResidualMode::Compat)
     std::printf("p == 1!\n");
+  if (rep.det_computed) {  // only with --det
+    if (std::isnan(rep.det.sign)) std::printf("slogdet: nan %.15e\n", rep.det.logabsdet);
+    else std::printf("slogdet: %d %.15e\n", (int)rep.det.sign, rep.det.logabsdet);
+  }
   if (rep.rhs_solved) {  // only with --rhs: the reference has no A x = b mode
     std::printf("solution x:\n");
     for (double v : rep.x_head) std::printf("%.2f\t", v);

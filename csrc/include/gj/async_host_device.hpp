@@ -117,6 +117,8 @@ class AsyncHostDevice : public Device {
   void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) override;
   void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw, bool w_natural,
                    const double* Z, int64_t ldz, int64_t k, double sign, int s) override;
+  void slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb, const int32_t* which,
+                     double* sign, double* logabs, int s) override;
 
   // A fence between queues: signalled by the stream that records it, waited on by any stream
   // (of any AsyncHostDevice of this process) or by the host.

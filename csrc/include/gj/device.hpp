@@ -473,6 +473,26 @@ class Device {
   // refused with Status::BadArgs.
   virtual void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw,
                            bool w_natural, const double* Z, int64_t ldz, int64_t k, double sign, int s) = 0;
+
+  // ---- determinants of small blocks (Engine::slogdet over the stashed pivot-block inverses) ----
+  // For b < nb: (sign[b], logabs[b]) = slogdet of the m x m block at blocks + b*stride (dtype dt, ld m).
+  // Worked in fp64 whatever dt is (an fp32 block is widened exactly).  LU with partial pivoting:
+  // sign = (-1)^swaps * prod sgn(pivot), logabs = sum log|pivot|, both as double.
+  // A NaN or Inf in the block gives sign = logabs = NaN, wherever it stands (every entry is looked at
+  // before the first column); so does a pivot that overflows on the way.
+  // Otherwise an exactly zero pivot gives sign 0, logabs -inf (numpy's convention).
+  // The input is not written.
+  // which (int32[nb], device, or null): blocks with which[b] == 0 are skipped and their outputs are left
+  // untouched.
+  // No atomics: two launches on the same input give the same bits.
+  // GPU: m <= 128 runs in LDS; a larger m in an fp64 copy in device scratch that the device keeps and
+  // grows on demand, which waits for the device: a caller that must not allocate mid-stream asks for it
+  // ahead with prepare_slogdet.  slogdet_scratch_bytes(m, nb) is the size of that scratch for such a
+  // launch (0: none needed), for the caller's memory estimate.
+  virtual void slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb,
+                             const int32_t* which, double* sign, double* logabs, int s) = 0;
+  virtual size_t slogdet_scratch_bytes(int64_t m, int64_t nb) const { (void)m; (void)nb; return 0; }
+  virtual void prepare_slogdet(int64_t m, int64_t nb) { (void)m; (void)nb; }
 };
 
 // Test probe of Device::panel_rhs, like g_last_gemm_kernel: "host" on the host executor,
@@ -482,5 +502,7 @@ inline thread_local const char* g_last_rhs_kernel = "";
 inline thread_local const char* g_last_rhs_t_kernel = "";
 // The same of Device::rank_update: "host", or "rku<k padded to 4>:<f64|f32>:<vec|scalar>".
 inline thread_local const char* g_last_rank_update_kernel = "";
+// The same of Device::slogdet_batch: "host", or "sld:<lds|glob>:<f64|f32>".
+inline thread_local const char* g_last_slogdet_kernel = "";
 
 }  // namespace gj

@@ -79,6 +79,10 @@ struct SolveOptions {
   bool verify = false;
   double comm_timeout_s = 600;  // a host wait on a pivot longer than this is a peer failure
   int reserve_cus = -1;     // CUs kept free of the trailing update for the pivot path (-1 = auto)
+  // Keep what Engine::slogdet needs: every step's H_t = inv(P_t) is copied into a stash of Nr blocks
+  // (m * m elements each, counted in the work space) by the chunk pass on COMM before Ht_ is reused.
+  // Off (default): allocation, launches and results are exactly those of an engine without it.
+  bool track_det = false;
 };
 
 // Device time per phase (sum over the solve; phases on different streams overlap in time).
@@ -139,6 +143,21 @@ struct UpdateResult {
   double min_pivot = 0;          // smallest |pivot| of the LU of C = I + V^T inv(A) U, over max(1, max|C - I|)
   double cond1 = 0;              // ||C||_1 ||inv(C)||_1 (0 when refused)
   double seconds = 0;            // this rank's wall time of the call
+  // slogdet of C, from the pivots and the row swaps of its LU: det(A + U V^T) = det(C) det(A).
+  // Meaningless when the update was refused (the LU stopped at the offending pivot).
+  double sign_c = 0;
+  double logabsdet_c = 0;
+};
+
+// Result of Engine::slogdet.
+struct DetResult {
+  Status status = Status::Ok;    // BadArgs: no successful solve() with SolveOptions::track_det to take it from
+  // -1 or +1; NaN (with logabsdet NaN) when a stashed H_t holds a non-finite entry or is exactly
+  // singular, so that no determinant can be formed from it.  Never 0: a singular A fails solve(), and
+  // only the Python convenience gj.slogdet turns that failure into (0, -inf).
+  double sign = 0;
+  double logabsdet = 0;          // log|det|
+  double seconds = 0;            // this rank's wall time of the call (about 0 when the cached value is returned)
 };
 
 class Engine {
@@ -245,6 +264,18 @@ class Engine {
   UpdateResult update_inverse(const double* U, int64_t ldu, const double* V, int64_t ldv, int64_t k);
   // The same with U and V in device memory (fp64), e.g. torch CUDA tensors.
   UpdateResult update_inverse_device(const double* U_dev, int64_t ldu, const double* V_dev, int64_t ldv, int64_t k);
+  // sign and log|det| of the matrix whose inverse the result panel holds.  Collective; valid after a
+  // successful solve() with SolveOptions::track_det, else Status::BadArgs.  No rows are swapped and the
+  // padded system is diag(A, I), so with H_t the stashed inverse of step t's pivot block and sigma the
+  // block permutation t -> s_t (SolveStats::pivots)
+  //     det(A) = sgn(sigma)^m / prod_t det(H_t).
+  // One Device::slogdet_batch launch over the stash (det H^T = det H: the K-major blocks as they are),
+  // restricted to the steps this rank owns; 2 Nr doubles come back; the host adds -log|det H_t| and
+  // counts the negative signs in step order, Comm::allreduce_sum adds both over the ranks (the same
+  // bits on every rank), and sgn(sigma)^m comes from a cycle count of the pivots.
+  // The value is cached: update_inverse multiplies it by det(C) (computing it first if need be; a
+  // refused update leaves it alone), so it stays the determinant of the matrix the panel inverts.
+  DetResult slogdet();
   // Precision of the last residual: true = fp64 (always for fp64 solves; fp32 solves when it fits).
   bool residual_fp64() const { return last_residual_fp64_; }
   // ||A||_inf of the last solve's input (the reference's norm, taken at solve start) and
@@ -479,6 +510,17 @@ class Engine {
   double* dscratch_ = nullptr;
   uint64_t* vparts_ = nullptr;  // GJ_VERIFY: npanels x vslots x Device::kHashParts partial hashes
   int32_t* iscratch_ = nullptr;
+  // SolveOptions::track_det: the H_t of every step (Nr blocks of m * m), slogdet_batch's selection and
+  // its 2 Nr outputs followed by the kDetPart partial sums that go through the all-reduce; the last
+  // solve's pivots and the cached determinant
+  static constexpr int kDetPart = 3;
+  void* det_stash_ = nullptr;
+  int32_t* det_which_ = nullptr;
+  double* det_out_ = nullptr;
+  std::vector<int32_t> det_pivots_;
+  bool det_ready_ = false;   // the stash holds a finished solve's blocks
+  bool det_cached_ = false;  // det_ is current
+  DetResult det_;
   // pinned host
   PivotResult* piv_host_ = nullptr;
   int32_t* ihost_ = nullptr;

@@ -118,6 +118,10 @@ class HipDevice : public Device {
   void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) override;
   void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw, bool w_natural,
                    const double* Z, int64_t ldz, int64_t k, double sign, int s) override;
+  void slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb, const int32_t* which,
+                     double* sign, double* logabs, int s) override;
+  size_t slogdet_scratch_bytes(int64_t m, int64_t nb) const override;
+  void prepare_slogdet(int64_t m, int64_t nb) override;
 
  private:
   void* scratch(size_t bytes, int slot);
@@ -128,8 +132,9 @@ class HipDevice : public Device {
   int bi_hint_ = -1;  // set_block_inverse_hint
   int tile_hint_ = 0;  // set_gemm_tile_hint
   std::vector<void*> events_;
-  void* scratch_[4] = {nullptr, nullptr, nullptr, nullptr};  // 2, 3: panel_rhs / panel_rhs_t slice partials
-  size_t scratch_sz_[4] = {0, 0, 0, 0};
+  // 2, 3: panel_rhs / panel_rhs_t slice partials; 4: slogdet_batch's fp64 images (m > 128)
+  void* scratch_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t scratch_sz_[5] = {0, 0, 0, 0, 0};
 };
 
 }  // namespace gj

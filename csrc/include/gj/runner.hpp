@@ -89,6 +89,11 @@ struct RunReport {
   std::vector<RhsResult> rhs_cols;
   bool updated = false;             // RunConfig::update_u / update_v were applied
   UpdateResult update;              // rank 0's result of it
+  // SolveOptions::track_det: Engine::slogdet after the inversion (and after the update, if any), rank
+  // 0's result and every rank's (sign, logabsdet) pair, which must agree bit for bit
+  bool det_computed = false;
+  DetResult det;
+  std::vector<double> det_ranks;    // 2 * ranks
   // race_check: unordered conflicting accesses found (total, the first distinct ones described),
   // ops checked
   int64_t race_count = 0;

@@ -164,5 +164,13 @@ void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* 
                  const double* Z, int64_t ldz, int64_t k, double sign, hipStream_t s);
 const char* last_rank_update_kernel();
 
+// slogdet.hip: Device::slogdet_batch.  scratch: slogdet_scratch_bytes(m, nb) bytes (0 for m <= 128, the
+// LDS form).  Test probe: the name of this thread's last launch, "sld:<lds|glob>:<f64|f32>" ("host" on
+// the host executor).
+size_t slogdet_scratch_bytes(int64_t m, int64_t nb);
+void slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb, const int32_t* which,
+                   double* sign, double* logabs, void* scratch, hipStream_t s);
+const char* last_slogdet_kernel();
+
 }  // namespace kern
 }  // namespace gj

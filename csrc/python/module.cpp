@@ -254,6 +254,9 @@ PYBIND11_MODULE(_C, mod) {
   mod.def("last_rank_update_kernel", [] { return std::string(kern::last_rank_update_kernel()); },
           "test probe: 'rku<k padded to 4>:<f64|f32>:<vec|scalar>' of this thread's last Device.rank_update "
           "('host' on the host executor)");
+  mod.def("last_slogdet_kernel", [] { return std::string(kern::last_slogdet_kernel()); },
+          "test probe: 'sld:<lds|glob>:<f64|f32>' of this thread's last Device.slogdet_batch ('host' on the "
+          "host executor)");
   mod.def("set_lat_glds", [](bool on) { kern::set_lat_glds(on ? 1 : 0); },
           "every latency GEMM of >= 1024 rows on the LDS-DMA kernel (tests; the engine sets it per launch)");
 
@@ -634,6 +637,18 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("dt"), py::arg("X"), py::arg("ldx"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"),
            py::arg("W"), py::arg("ldw"), py::arg("w_natural"), py::arg("Z"), py::arg("ldz"), py::arg("ncols"),
            py::arg("sign"))
+      // (sign, log|det|) of nb blocks of m x m (dtype dt, stride elements apart); which: int32[nb] or 0
+      .def("slogdet_batch",
+           [](Device& d, const std::string& dt, U blocks, int64_t stride, int64_t m, int64_t nb, U which, U sign,
+              U logabs) {
+             py::gil_scoped_release rel;
+             d.slogdet_batch(parse_dtype(dt), (const void*)blocks, stride, m, nb, (const int32_t*)which,
+                             (double*)sign, (double*)logabs, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("dt"), py::arg("blocks"), py::arg("stride"), py::arg("m"), py::arg("nb"), py::arg("which"),
+           py::arg("sign"), py::arg("logabs"))
+      .def("slogdet_scratch_bytes", [](Device& d, int64_t m, int64_t nb) { return d.slogdet_scratch_bytes(m, nb); })
       .def("axpy_cols_masked",
            [](Device& d, U Y, int64_t ldy, U C_in, int64_t ldc, U S, int64_t lds, double sign, int64_t rows,
               int64_t ncols, U active, U colmax) {
@@ -826,8 +841,9 @@ PYBIND11_MODULE(_C, mod) {
       .def(py::init([](std::shared_ptr<Device> dev, std::shared_ptr<Comm> comm, int64_t n, int64_t m,
                        const std::string& dtype, int64_t chunk_cols, double eps, bool sync_debug,
                        int depth, bool profile, double comm_timeout_s, const std::string& pivot,
-                       double pivot_growth) {
+                       double pivot_growth, bool track_det) {
              SolveOptions o;
+             o.track_det = track_det;
              o.pivot_growth = pivot_growth;
              o.dtype = parse_dtype(dtype);
              o.depth = depth;
@@ -846,7 +862,24 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("device"), py::arg("comm"), py::arg("n"), py::arg("m"), py::arg("dtype") = "fp64",
            py::arg("chunk_cols") = 0, py::arg("eps") = kDefaultEps, py::arg("sync_debug") = false,
            py::arg("depth") = 0, py::arg("profile") = false, py::arg("comm_timeout_s") = 600.0,
-           py::arg("pivot") = "block-min-inv-norm", py::arg("pivot_growth") = -1.0)
+           py::arg("pivot") = "block-min-inv-norm", py::arg("pivot_growth") = -1.0,
+           py::arg("track_det") = false)
+      .def("slogdet",
+           [](PyEngine& e) {
+             DetResult dr;
+             {
+               py::gil_scoped_release rel;
+               dr = e.eng->slogdet();
+             }
+             py::dict d;
+             d["status"] = (int)dr.status;
+             d["sign"] = dr.sign;
+             d["logabsdet"] = dr.logabsdet;
+             d["seconds"] = dr.seconds;
+             return d;
+           },
+           "sign and log|det| of the matrix the result panel inverts (Engine::slogdet; collective): valid after a "
+           "successful solve() of an engine built with track_det=True, else status 5 (BadArgs)")
       .def_property_readonly("layout",
                              [](PyEngine& e) {
                                const Layout& L = e.eng->layout();
@@ -1029,6 +1062,8 @@ PYBIND11_MODULE(_C, mod) {
              info["min_pivot"] = ur.min_pivot;
              info["cond1"] = ur.cond1;
              info["seconds"] = ur.seconds;
+             info["sign_c"] = ur.sign_c;
+             info["logabsdet_c"] = ur.logabsdet_c;
              return info;
            },
            py::arg("U") = py::none(), py::arg("V") = py::none(), py::arg("u_dev") = 0, py::arg("ldu") = 0,
@@ -1203,6 +1238,7 @@ PYBIND11_MODULE(_C, mod) {
     if (d.contains("refine")) c.refine = d["refine"].cast<int>();
     if (d.contains("refine_tol")) c.refine_tol = d["refine_tol"].cast<double>();
     if (d.contains("race_check")) c.race_check = d["race_check"].cast<bool>();
+    if (d.contains("det")) c.solve.track_det = d["det"].cast<bool>();
     py::array_t<double, py::array::c_style | py::array::forcecast> inp;
     if (d.contains("input") && !d["input"].is_none()) {
       inp = d["input"].cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
@@ -1260,6 +1296,10 @@ PYBIND11_MODULE(_C, mod) {
       u["cond1"] = r.update.cond1;
       u["seconds"] = r.update.seconds;
       o["update"] = u;
+    }
+    if (r.det_computed) {
+      o["slogdet"] = std::vector<double>{r.det.sign, r.det.logabsdet};
+      o["slogdet_ranks"] = to_array(r.det_ranks, c.ranks, 2);
     }
     if (r.rhs_solved) {
       o["axb_residual"] = r.rhs_residual;

@@ -373,5 +373,11 @@ void AsyncHostDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& 
   g_last_rank_update_kernel = "host";
   enqueue(s, [=] { inner_.rank_update(dt, X, ldx, L, W, ldw, w_natural, Z, ldz, k, sign, s); });
 }
+void AsyncHostDevice::slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb,
+                                    const int32_t* which, double* sign, double* logabs, int s) {
+  GJ_REQUIRE(m >= 1 && nb >= 0 && stride >= m * m, "slogdet_batch: m >= 1, nb >= 0, stride >= m * m");
+  g_last_slogdet_kernel = "host";
+  enqueue(s, [=] { inner_.slogdet_batch(dt, blocks, stride, m, nb, which, sign, logabs, s); });
+}
 
 }  // namespace gj

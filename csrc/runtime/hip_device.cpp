@@ -447,4 +447,16 @@ void HipDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& L, con
   check_launch();
 }
 
+size_t HipDevice::slogdet_scratch_bytes(int64_t m, int64_t nb) const { return kern::slogdet_scratch_bytes(m, nb); }
+void HipDevice::prepare_slogdet(int64_t m, int64_t nb) {
+  const size_t b = kern::slogdet_scratch_bytes(m, nb);
+  if (b) scratch(b, 4);
+}
+void HipDevice::slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb,
+                              const int32_t* which, double* sign, double* logabs, int s) {
+  const size_t b = kern::slogdet_scratch_bytes(m, nb);
+  kern::slogdet_batch(dt, blocks, stride, m, nb, which, sign, logabs, b ? scratch(b, 4) : nullptr, hs(streams_[s]));
+  check_launch();
+}
+
 }  // namespace gj

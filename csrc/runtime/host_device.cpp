@@ -677,4 +677,57 @@ void HostDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& L, co
   });
 }
 
+void HostDevice::slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb,
+                               const int32_t* which, double* sign, double* logabs, int) {
+  GJ_REQUIRE(m >= 1 && nb >= 0 && stride >= m * m, "slogdet_batch: m >= 1, nb >= 0, stride >= m * m");
+  g_last_slogdet_kernel = "host";
+  parallel_for(nb, nthreads_, [&](int64_t b) {
+    if (which && which[b] == 0) return;
+    std::vector<double> a((size_t)(m * m));  // the fp64 copy: the input is not written
+    bool bad = false;  // a NaN or an Inf entry: (NaN, NaN) whatever the pivots would do
+    for (int64_t e = 0; e < m * m; ++e) {
+      a[(size_t)e] = dt == DType::F64 ? tp<double>(blocks)[b * stride + e] : (double)tp<float>(blocks)[b * stride + e];
+      bad = bad || !std::isfinite(a[(size_t)e]);
+    }
+    if (bad) {
+      sign[b] = logabs[b] = std::numeric_limits<double>::quiet_NaN();
+      return;
+    }
+    std::vector<int64_t> perm((size_t)m);
+    for (int64_t i = 0; i < m; ++i) perm[(size_t)i] = i;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    double sg = 1.0, lg = 0.0;
+    for (int64_t c = 0; c < m; ++c) {
+      // the largest magnitude of column c over the unused rows, NaN above everything, the first among equals
+      int64_t ps = c;
+      double pa = std::fabs(a[(size_t)(perm[(size_t)c] * m + c)]);
+      for (int64_t i = c + 1; i < m && !std::isnan(pa); ++i) {
+        const double v = std::fabs(a[(size_t)(perm[(size_t)i] * m + c)]);
+        if (std::isnan(v) || v > pa) pa = v, ps = i;
+      }
+      if (ps != c) std::swap(perm[(size_t)ps], perm[(size_t)c]), sg = -sg;
+      const double* prow = &a[(size_t)(perm[(size_t)c] * m)];
+      const double piv = prow[c];
+      if (!std::isfinite(piv)) {
+        sg = lg = nan;
+        break;
+      }
+      if (piv == 0.0) {
+        sg = 0.0;
+        lg = -std::numeric_limits<double>::infinity();
+        break;
+      }
+      lg += std::log(std::fabs(piv));
+      if (piv < 0.0) sg = -sg;
+      for (int64_t i = c + 1; i < m; ++i) {
+        double* row = &a[(size_t)(perm[(size_t)i] * m)];
+        const double l = row[c] / piv;
+        for (int64_t j = c + 1; j < m; ++j) row[j] -= l * prow[j];
+      }
+    }
+    sign[b] = sg;
+    logabs[b] = lg;
+  });
+}
+
 }  // namespace gj

@@ -828,5 +828,21 @@ void RaceCheckDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& 
   check(s, "rank_update", a);
   inner_->rank_update(dt, X, ldx, L, Wm, ldw, w_natural, Z, ldz, k, sign, s);
 }
+void RaceCheckDevice::slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb,
+                                    const int32_t* which, double* sign, double* logabs, int s) {
+  std::vector<Acc> a;
+  if (m >= 1 && nb > 0 && stride >= m * m) {  // (the inner device refuses anything else before it touches memory)
+    const int64_t es = (int64_t)dtype_size(dt);
+    // The selection is device data that cannot be read here without waiting for the stream (which
+    // would change the schedule under check): every block is declared read and both outputs written
+    // whole, a superset of what a launch with a selection touches -- it can add a report, never hide one.
+    if (which) a.push_back(R(span(which, 4 * nb), "which"));
+    a.push_back(R(rect(blocks, stride, m * m, nb, es), "blocks"));
+    a.push_back(W(span(sign, 8 * nb), "sign"));
+    a.push_back(W(span(logabs, 8 * nb), "logabs"));
+  }
+  check(s, "slogdet_batch", a);
+  inner_->slogdet_batch(dt, blocks, stride, m, nb, which, sign, logabs, s);
+}
 
 }  // namespace gj

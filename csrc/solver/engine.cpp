@@ -371,10 +371,13 @@ int Engine::alloc_buffers(std::string& why) {
   int64_t wmax = 0;
   for (size_t c = 0; c < cb0_.size(); ++c) wmax = std::max(wmax, chunk_w((int64_t)c));
   const size_t need_matrix = 2 * panel;
-  const size_t need_work = 3 * (size_t)dm * rows * es + 2 * (size_t)dm * npad * es + 4 * (size_t)dm * dm * es +
-                           (size_t)m * dm * es +
-                           (size_t)std::max<int64_t>(L_.nblk, 1) * m * m * es + (size_t)m * wmax * es +
-                           dev_.block_inverse_scratch_bytes(opt_.dtype, L_, bi_hint_);
+  size_t need_work = 3 * (size_t)dm * rows * es + 2 * (size_t)dm * npad * es + 4 * (size_t)dm * dm * es +
+                     (size_t)m * dm * es +
+                     (size_t)std::max<int64_t>(L_.nblk, 1) * m * m * es + (size_t)m * wmax * es +
+                     dev_.block_inverse_scratch_bytes(opt_.dtype, L_, bi_hint_);
+  if (opt_.track_det)  // the H_t stash, slogdet_batch's selection, outputs and scratch: Nr is every rank's
+    need_work += (size_t)L_.Nr * m * m * es + (size_t)L_.Nr * (2 * sizeof(double) + sizeof(int32_t)) +
+                 kDetPart * sizeof(double) + dev_.slogdet_scratch_bytes(m, L_.Nr);
   const size_t avail = dev_.on_gpu() ? dev_.free_memory() : SIZE_MAX;
   auto fits = [&](size_t need) { return !dev_.on_gpu() || need + (64u << 20) <= avail; };
   // stage 1: the matrix panels (the reference's a / b arrays)
@@ -439,6 +442,12 @@ void Engine::alloc_work(int64_t wmax) {
   }
   // the candidate-inverse kernel's scratch, now: not lazily inside the first timed pivot search
   dev_.prepare_block_inverse(opt_.dtype, L_, bi_hint_);
+  if (opt_.track_det) {
+    det_stash_ = dev_.alloc((size_t)L_.Nr * m * m * es);
+    det_which_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * L_.Nr));
+    det_out_ = static_cast<double*>(dev_.alloc(sizeof(double) * (2 * L_.Nr + kDetPart)));
+    dev_.prepare_slogdet(m, L_.Nr);
+  }
   scores_ = static_cast<double*>(dev_.alloc(sizeof(double) * std::max<int64_t>(L_.nblk, 1)));
   valid_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * std::max<int64_t>(L_.nblk, 1)));
   pos_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * L_.Nr));
@@ -497,7 +506,7 @@ void Engine::label_work() {
       {valid_, "valid"}, {pos_, "pos"}, {phys_at_, "phys_at"}, {used_, "used"}, {seq_, "seq"}, {myrec_, "myrec"},
       {sel_done_, "sel_done"}, {recs_, "recs"}, {piv_dev_, "piv_dev"}, {dscratch_, "dscratch"},
       {iscratch_, "iscratch"}, {piv_host_, "piv_host"}, {ihost_, "ihost"}, {dhost_, "dhost"},
-      {vparts_, "vparts"}};
+      {vparts_, "vparts"}, {det_stash_, "det_stash"}, {det_which_, "det_which"}, {det_out_, "det_out"}};
   for (const auto& nv : named)
     if (nv.first) dev_.label(nv.first, nv.second);
 }
@@ -512,7 +521,8 @@ void Engine::free_work() {
                                reinterpret_cast<void**>(&sel_done_),
                                reinterpret_cast<void**>(&recs_), reinterpret_cast<void**>(&piv_dev_),
                                reinterpret_cast<void**>(&dscratch_), reinterpret_cast<void**>(&iscratch_),
-                               reinterpret_cast<void**>(&vparts_)};
+                               reinterpret_cast<void**>(&vparts_), &det_stash_,
+                               reinterpret_cast<void**>(&det_which_), reinterpret_cast<void**>(&det_out_)};
   for (int i = 0; i < 3; ++i) dptrs.push_back(&At_[i]);
   for (int i = 0; i < 2; ++i) {
     dptrs.push_back(&Rb_[i]);
@@ -1215,6 +1225,12 @@ void Engine::chunk_pipeline(int64_t v, bool wait_main) {
       dev_.memset2d(chunk + (corrupt_step_ - t0) * m * W * (int64_t)es, W * es, W * es, m, S_COMM);
     dev_.record(ev_b_[par][c], S_COMM);
   }
+  // SolveOptions::track_det: the H_t of the steps this rank owns into their stash slots, behind the
+  // pass's last read of Ht_ and ahead of ev_cp_, the edge that already guards the reuse of Ht_
+  if (det_stash_)
+    for (int64_t j = 0; j < q; ++j)
+      if (piv_[par][j].owner == L_.k)
+        dev_.copy(elem(det_stash_, (t0 + j) * m * m), Ht_[par][j], (size_t)m * m * es, S_COMM);
   if (vlocal_on()) vlocal_hash(v, V_LE, false, S_COMM);  // ... and after its last read
   dev_.record(ev_cp_[par], S_COMM);
   dbg_sync();
@@ -1425,6 +1441,7 @@ SolveStats Engine::solve() {
 
 SolveStats Engine::solve_steps() {
   GJ_REQUIRE(!solved_, "solve(): input panel already consumed; load the matrix again");
+  det_ready_ = det_cached_ = false;
   cur_step_ = -1;
   cur_phase_ = "norm";
   SolveStats st;
@@ -1465,6 +1482,7 @@ SolveStats Engine::solve_steps() {
   dev_.copy(seq_, ihost_ + Nr, sizeof(int32_t) * Nr, S_SIDE);
   if (vparts_)
     dev_.memset0(vparts_, sizeof(uint64_t) * Device::kHashParts * (size_t)npanels() * (size_t)vslots(), S_SIDE);
+  if (det_stash_) dev_.memset0(det_stash_, (size_t)Nr * m * m * esz(), S_SIDE);
   dev_.sync_stream(S_SIDE);
 
   st.pivots.assign(Nr, -1);
@@ -1518,7 +1536,69 @@ SolveStats Engine::solve_steps() {
   st.seconds = t_end - t_begin;
   prof_collect(st);
   solved_ = true;
+  if (det_stash_) {
+    det_pivots_ = st.pivots;
+    det_ready_ = true;
+  }
   return st;
+}
+
+// ---------------------------------------------------------------- det(A) from the pivot blocks
+DetResult Engine::slogdet() {
+  DetResult out;
+  if (!opt_.track_det || !det_ready_) {
+    out.status = Status::BadArgs;
+    return out;
+  }
+  if (det_cached_) {
+    out = det_;
+    out.seconds = 0;
+    return out;
+  }
+  const double t0 = now_s();
+  const int64_t m = L_.m, Nr = L_.Nr;
+  std::vector<int32_t> which((size_t)Nr);
+  for (int64_t t = 0; t < Nr; ++t) which[(size_t)t] = det_pivots_[(size_t)t] % L_.p == L_.k ? 1 : 0;
+  std::vector<double> res((size_t)(2 * Nr), 0.0);
+  dev_.copy(det_which_, which.data(), sizeof(int32_t) * (size_t)Nr, S_MAIN);
+  dev_.slogdet_batch(opt_.dtype, det_stash_, m * m, m, Nr, det_which_, det_out_, det_out_ + Nr, S_MAIN);
+  dev_.copy(res.data(), det_out_, sizeof(double) * 2 * (size_t)Nr, S_MAIN);
+  comm_.drain(dev_, S_MAIN);
+  // this rank's steps, in step order: -log|det H_t|, the negative signs, the blocks without a sign
+  // (0: an exactly singular H_t; NaN: a non-finite one)
+  double part[kDetPart] = {0.0, 0.0, 0.0};
+  for (int64_t t = 0; t < Nr; ++t) {
+    if (!which[(size_t)t]) continue;
+    const double sg = res[(size_t)t];
+    part[0] -= res[(size_t)(Nr + t)];
+    if (sg < 0) part[1] += 1.0;
+    else if (!(sg > 0)) part[2] += 1.0;
+  }
+  double* dpart = det_out_ + 2 * Nr;  // its own kDetPart doubles behind the 2 Nr outputs
+  dev_.copy(dpart, part, sizeof(part), S_MAIN);
+  comm_.allreduce_sum(dev_, dpart, kDetPart, DType::F64, S_MAIN);
+  dev_.copy(part, dpart, sizeof(part), S_MAIN);
+  comm_.drain(dev_, S_MAIN);
+  // sgn(sigma) = (-1)^(Nr - cycles)
+  int64_t cycles = 0;
+  std::vector<char> seen((size_t)Nr, 0);
+  for (int64_t t = 0; t < Nr; ++t) {
+    if (seen[(size_t)t]) continue;
+    ++cycles;
+    for (int64_t u = t; !seen[(size_t)u]; u = det_pivots_[(size_t)u]) seen[(size_t)u] = 1;
+  }
+  const bool sigma_odd = ((Nr - cycles) & 1) != 0;
+  const bool neg = (((int64_t)part[1] & 1) != 0) != (sigma_odd && (m & 1));
+  if (part[2] > 0 || std::isnan(part[0])) {
+    out.sign = out.logabsdet = std::numeric_limits<double>::quiet_NaN();
+  } else {
+    out.sign = neg ? -1.0 : 1.0;
+    out.logabsdet = part[0];
+  }
+  out.seconds = now_s() - t0;
+  det_ = out;
+  det_cached_ = true;
+  return out;
 }
 
 // ---------------------------------------------------------------- GJ_VERIFY

@@ -462,6 +462,8 @@ struct SmallInverse {
   double min_pivot = 0;
   std::vector<double> inv;  // inv(C), k x k (zeros when singular)
   double cond1 = 0;         // ||C||_1 ||inv(C)||_1 (0 when the LU already refused)
+  // slogdet(C) from the LU's pivots and row swaps (0, -inf at a zero pivot; NaN, NaN at a non-finite one)
+  double sign = 1.0, logabs = 0.0;
 };
 
 // C = I + T (k x k, row-major) by an LU with partial pivoting in fp64, inv(C) column by column.
@@ -479,6 +481,7 @@ SmallInverse invert_small(const std::vector<double>& T, int64_t k, double eps, d
   std::vector<int64_t> perm((size_t)k);
   for (int64_t i = 0; i < k; ++i) perm[(size_t)i] = i;
   bool singular = !std::isfinite(scale);
+  if (singular) out.sign = out.logabs = std::numeric_limits<double>::quiet_NaN();
   double minpiv = std::numeric_limits<double>::infinity();
   for (int64_t c = 0; c < k && !singular; ++c) {
     int64_t pr = c;
@@ -487,8 +490,18 @@ SmallInverse invert_small(const std::vector<double>& T, int64_t k, double eps, d
     if (pr != c) {
       for (int64_t j = 0; j < k; ++j) std::swap(C[(size_t)(c * k + j)], C[(size_t)(pr * k + j)]);
       std::swap(perm[(size_t)c], perm[(size_t)pr]);
+      out.sign = -out.sign;
     }
     const double piv = C[(size_t)(c * k + c)];
+    if (!std::isfinite(piv)) {
+      out.sign = out.logabs = std::numeric_limits<double>::quiet_NaN();
+    } else if (piv == 0.0) {
+      out.sign = 0.0;
+      out.logabs = -std::numeric_limits<double>::infinity();
+    } else {
+      out.logabs += std::log(std::fabs(piv));
+      if (piv < 0.0) out.sign = -out.sign;
+    }
     if (!std::isfinite(piv) || std::fabs(piv) <= eps * scale) {
       singular = true;
       minpiv = std::isfinite(piv) ? std::min(minpiv, std::fabs(piv) / scale) : 0.0;
@@ -546,6 +559,8 @@ UpdateResult Engine::update_inverse(const double* U, int64_t ldu, const double* 
   const int64_t n = L_.n, rows = L_.rows;
   UpdateResult out;
   out.k = k;
+  // the determinant follows the panel: take det(A) from the stash before the first update moves on
+  if (opt_.track_det && !det_cached_) slogdet();
   BufSet bufs(dev_);
   const size_t nat = (size_t)std::max<int64_t>(n, 1) * k, loc = (size_t)std::max<int64_t>(rows, 1) * k;
   double* Ud = bufs.get<double>(nat);    // U, V, Z = X^T V: natural row order, ld k
@@ -569,6 +584,8 @@ UpdateResult Engine::update_inverse(const double* U, int64_t ldu, const double* 
   for (double v : T) tmax = max_keep_nan(tmax, std::fabs(v));
   const SmallInverse ci = invert_small(T, k, opt_.eps, std::isfinite(tmax) ? std::max(1.0, tmax) : tmax);
   out.min_pivot = ci.min_pivot;
+  out.sign_c = ci.sign;
+  out.logabsdet_c = ci.logabs;
   // one outcome for all ranks, before anything is written
   if (comm_.host_max(dev_, ci.singular ? 1.0 : 0.0) > 0) {
     out.status = Status::Singular;
@@ -581,6 +598,10 @@ UpdateResult Engine::update_inverse(const double* U, int64_t ldu, const double* 
     dev_.gemm(DType::F64, GemmOp::Store, ALayout::RowMajor, rows, k, k, Wl, k, Cd, k, Wc, k, S_MAIN);
   dev_.rank_update(opt_.dtype, out_, L_.npad, L_, Wc, k, false, Z, k, k, -1.0, S_MAIN);
   comm_.drain(dev_, S_MAIN);  // (ci.inv is read by the copy until here)
+  if (det_cached_) {  // det(A + U V^T) = det(C) det(A)
+    det_.sign *= ci.sign;
+    det_.logabsdet += ci.logabs;
+  }
   out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return out;
 }

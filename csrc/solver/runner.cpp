@@ -177,6 +177,15 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
       sh.rep.update = ur;
     }
   }
+  if (cfg.solve.track_det) {
+    const DetResult dr = eng->slogdet();
+    std::lock_guard<std::mutex> lk(sh.mu);
+    sh.rep.det_computed = true;
+    sh.rep.det_ranks.resize((size_t)(2 * cfg.ranks));
+    sh.rep.det_ranks[(size_t)(2 * rank)] = dr.sign;
+    sh.rep.det_ranks[(size_t)(2 * rank + 1)] = dr.logabsdet;
+    if (rank == 0) sh.rep.det = dr;
+  }
   if (cfg.want_corners) {
     auto c = eng->corner(nm, 1);
     if (rank == 0) {

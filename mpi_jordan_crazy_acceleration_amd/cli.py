@@ -11,6 +11,8 @@ its corner, ``glob_time: %.2f`` (max over ranks), ``inverse matrix:`` + blank li
 corner, ``residual: %e`` (or ``p == 1!`` with ``--residual compat`` on one rank).  Exit codes:
 0 ok, 1 usage, 2 any failure (cannot open / cannot read / singular matrix / not enough memory).
 The in-process ``build/gj`` binary is the same contract with threads instead of processes.
+``--det``: one more line after the residual line, ``slogdet: <sign> <logabsdet>`` (the determinant
+from the pivot blocks, ``DistributedGaussJordan.slogdet``), and ``"slogdet"`` in ``--json``.
 ``--comm-timeout S``: a rank waiting longer than S seconds on a peer fails (every rank, naming the
 step, phase and collective).  ``--same-gpu``: rehearse the p-rank RCCL path with every rank on
 GPU 0 (each rank its own RCCL host over loopback sockets; functional check, not a timing).
@@ -65,6 +67,7 @@ def main(argv=None) -> int:
     ap.add_argument("--comm-timeout", type=float, default=600.0)
     ap.add_argument("--bcast", choices=["auto", "ring", "direct"], default=None)
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--det", action="store_true")
     ap.add_argument("--same-gpu", action="store_true")
     try:
         args, unknown = ap.parse_known_args(argv)
@@ -117,7 +120,8 @@ def main(argv=None) -> int:
         try:
             solver = DistributedGaussJordan(n, m, dtype=args.dtype, chunk_cols=args.chunk_cols, eps=args.eps,
                                             host_threads=args.host_threads, depth=args.depth, pivot=args.pivot,
-                                            local_rank=local if gpu else None, comm_timeout=args.comm_timeout)
+                                            local_rank=local if gpu else None, comm_timeout=args.comm_timeout,
+                                            det=args.det)
         except C.GJError as e:  # agreed on every rank inside the constructor
             out("Not enough memory!\n" if e.status == 2 else f"error: {e}\n")
             return 2
@@ -167,12 +171,19 @@ def main(argv=None) -> int:
             out(f"residual: {res:e}\n")
         elif args.residual == "compat":
             out("p == 1!\n")
+        sld = None
+        if args.det:  # as build/gj --det: one line after the residual line
+            sld = solver.slogdet()
+            sign = "nan" if sld[0] != sld[0] else f"{int(sld[0]):d}"
+            out(f"slogdet: {sign} {sld[1]:.15e}\n")
         if args.json and rank == 0:
-            print(json.dumps({"n": n, "m": m, "ranks": world, "device": "gpu" if gpu else "cpu",
-                              "dtype": args.dtype, "status": st["status"], "glob_time": glob,
-                              "gflops_nominal": 2.0 * n ** 3 / glob / 1e9 if glob > 0 else 0.0,
-                              "residual": res, "offdiag_pivots": st["offdiag_pivots"]}),
-                  file=sys.stderr, flush=True)
+            rec = {"n": n, "m": m, "ranks": world, "device": "gpu" if gpu else "cpu",
+                   "dtype": args.dtype, "status": st["status"], "glob_time": glob,
+                   "gflops_nominal": 2.0 * n ** 3 / glob / 1e9 if glob > 0 else 0.0,
+                   "residual": res, "offdiag_pivots": st["offdiag_pivots"]}
+            if sld is not None:
+                rec["slogdet"] = [v if v - v == 0 else None for v in sld]  # JSON has no NaN or Infinity
+            print(json.dumps(rec), file=sys.stderr, flush=True)
         return 0
     finally:
         dist.destroy_process_group()

@@ -51,6 +51,7 @@ class GaussJordan:
     residual: str = "always"
     host_threads: int = 0
     race_check: bool = False  # happens-before schedule checker (RaceCheckDevice): report["races"]
+    det: bool = False  # keep the pivot blocks for Engine::slogdet (SolveOptions::track_det)
     extra: dict = field(default_factory=dict)
 
     def _cfg(self, n: int) -> dict:
@@ -62,13 +63,15 @@ class GaussJordan:
                    sync_debug=bool(self.sync_debug), residual=self.residual,
                    host_threads=int(self.host_threads), jitter_us=float(self.jitter_us),
                    race_check=bool(self.race_check))
+        if self.det:
+            cfg["det"] = True
         cfg.update(self.extra)
         return cfg
 
     def run(self, n: int, gen: str = "absdiff", seed: int = 0, file: Optional[str] = None,
             input: Optional[np.ndarray] = None, keep_inverse: bool = False, repeats: int = 1,
             rhs=None, keep_solution: bool = False, profile: bool = False, nrhs: int = 1,
-            trans: bool = False, update=None) -> dict:
+            trans: bool = False, update=None, det: bool = False) -> dict:
         """One CLI-equivalent run.  ``rhs``: None, "ones", "random", a file path, an n-vector or an
         n x k matrix — then x = inv(A) b is computed on the devices, refined in fp64, and
         ``axb_residual`` = ||A x - b||_inf reported.  ``nrhs`` > 1 (implied by a matrix): the block
@@ -78,8 +81,13 @@ class GaussJordan:
         ``update`` = (U, V), n-vectors or n x k with k <= 64: after the inversion the inverse is
         updated to that of A + U V^T (Engine::update_inverse) and the ``rhs`` solve, the residual and
         ``keep_inverse`` all refer to A + U V^T; the report gains ``update`` = {k, min_pivot, cond1,
-        seconds}."""
+        seconds}.
+        ``det``: the report gains ``slogdet`` = [sign, logabsdet] of the matrix the inverse belongs to
+        (Engine::slogdet; after the update, if one is given) and ``slogdet_ranks``, every rank's pair
+        (ranks x 2: the same bits in every row)."""
         cfg = self._cfg(n)
+        if det:
+            cfg["det"] = True
         cfg.update(gen=gen, seed=int(seed), keep_inverse=keep_inverse, repeats=int(repeats),
                    keep_solution=bool(keep_solution), profile=bool(profile))
         if file is not None:
@@ -126,7 +134,7 @@ class GaussJordan:
         return inv
 
 
-    def _engine_resident(self, A: torch.Tensor):
+    def _engine_resident(self, A: torch.Tensor, track_det: bool = False):
         """The native engine, solved on a CUDA tensor's rows (copied device-to-device)."""
         if A.ndim != 2 or A.shape[0] != A.shape[1]:
             raise ValueError("A must be square")
@@ -137,7 +145,7 @@ class GaussJordan:
         idx = a.device.index if a.device.index is not None else torch.cuda.current_device()
         eng = C.Engine(_hip_device(idx), C.self_comm(), n, int(self.block_size), self.dtype,
                        int(self.chunk_cols), float(self.eps), bool(self.sync_debug), int(self.depth),
-                       pivot=self.pivot)
+                       pivot=self.pivot, track_det=bool(track_det or self.det))
         torch.cuda.synchronize(a.device)  # A may have been written on torch's stream
         eng.upload_rows_device(a.data_ptr(), a.stride(0))
         st = eng.solve()
@@ -210,7 +218,9 @@ class Factored:
     array or a CPU tensor runs one host rank.
     ``update(U, V)``: the handle becomes that of A + U V^T (rank k <= 64) by the matrix inversion
     lemma, one pass over the inverse instead of another inversion; ``updates`` counts the updates
-    applied since the inversion and ``last_update`` holds the last one's result."""
+    applied since the inversion and ``last_update`` holds the last one's result.
+    ``slogdet()`` / ``det()``: the determinant of the matrix the handle stands for, from the pivot
+    blocks the inversion already computed (no second factorisation); they follow every ``update``."""
 
     def __init__(self, gj: "GaussJordan", A):
         self._is_torch = isinstance(A, torch.Tensor)
@@ -223,7 +233,7 @@ class Factored:
         self._a64_owned = False
         if self._is_torch and A.is_cuda:
             self._cuda = True
-            self._eng, self._a = gj._engine_resident(A)
+            self._eng, self._a = gj._engine_resident(A, track_det=True)
             self._a64 = A.detach().to(torch.float64).contiguous()
             self.n = int(A.shape[0])
             return
@@ -236,7 +246,7 @@ class Factored:
         self._a64 = np.ascontiguousarray(a)
         self._eng = C.Engine(C.host_device(int(gj.host_threads)), C.self_comm(), self.n, int(gj.block_size),
                              gj.dtype, int(gj.chunk_cols), float(gj.eps), bool(gj.sync_debug), int(gj.depth),
-                             pivot=gj.pivot)
+                             pivot=gj.pivot, track_det=True)
         self._eng.upload_local_rows(self._a64)
         st = self._eng.solve()
         if st["status"] == 1:
@@ -318,6 +328,23 @@ class Factored:
         self.last_update = res
         return res
 
+    def slogdet(self):
+        """(sign, log|det|) of the handle's matrix as Python floats, numpy.linalg.slogdet's convention:
+        det = sign * exp(logabsdet).  From the inverses of the pivot blocks that the inversion kept
+        (Engine::slogdet), times det(I + V^T inv(A) U) of every ``update`` since (the determinant
+        lemma), so it is valid after any number of updates."""
+        d = self._eng.slogdet()
+        if d["status"] != 0:
+            raise RuntimeError(STATUS.get(d["status"], "error"))
+        return float(d["sign"]), float(d["logabsdet"])
+
+    def det(self) -> float:
+        """sign * exp(logabsdet).  Overflows to +-inf (and underflows to 0) where the determinant leaves
+        the fp64 range, as numpy.linalg.det does: prefer ``slogdet`` for anything large."""
+        sign, logabs = self.slogdet()
+        with np.errstate(over="ignore"):
+            return float(sign * np.exp(logabs))
+
     def inverse(self):
         if self._cuda:
             out = torch.empty_like(self._a)
@@ -346,6 +373,23 @@ def factor(A, block_size: int = 128, **kw) -> Factored:
     and ``F.inverse()`` all come from that one inversion (a forward plus an adjoint solve costs one
     inversion, not two)."""
     return GaussJordan(block_size=block_size, residual="never", **kw).factor(A)
+
+
+def slogdet(A, block_size: int = 128, **kw):
+    """(sign, log|det A|) as Python floats, by one block Gauss-Jordan inversion (:func:`factor`) -- the
+    determinant comes from the pivot blocks, not from a second factorisation.  A singular matrix
+    gives (0.0, -inf), numpy.linalg.slogdet's answer, instead of SingularMatrixError."""
+    try:
+        return factor(A, block_size=block_size, **kw).slogdet()
+    except SingularMatrixError:
+        return 0.0, float("-inf")
+
+
+def det(A, block_size: int = 128, **kw) -> float:
+    """det A = sign * exp(logabsdet) of :func:`slogdet`; +-inf on overflow, as numpy.linalg.det."""
+    sign, logabs = slogdet(A, block_size=block_size, **kw)
+    with np.errstate(over="ignore"):
+        return float(sign * np.exp(logabs))
 
 
 def solve(A, b, block_size: int = 128, trans: bool = False, **kw):

@@ -305,3 +305,28 @@ def col_abs_sum(X: torch.Tensor, out: torch.Tensor, n: int, m: int, p: int = 1, 
     assert out.dtype == torch.float64 and out.is_contiguous() and X.stride(-1) == 1
     device_for(out).col_abs_sum(_DT[X.dtype], _p(X), X.stride(0), n, m, p, k, _p(out))
     return out
+
+
+def slogdet_batch(blocks: torch.Tensor, which: torch.Tensor = None, sign: torch.Tensor = None,
+                  logabs: torch.Tensor = None):
+    """(sign, logabs) of the determinants of an (nb, m, m) batch (Device::slogdet_batch): an LU with
+    partial pivoting in fp64 whatever the dtype (fp32 is widened exactly), sign = -1 / 0 / +1 and
+    logabs = log|det| as fp64 tensors on the blocks' device; an exactly zero pivot gives (0, -inf), a
+    NaN or Inf entry (NaN, NaN).  ``blocks`` fp64 / fp32, CPU or CUDA, each block contiguous; it is
+    only read.  ``which`` (int32, nb): blocks with which[b] == 0 are skipped and their entries of
+    ``sign`` / ``logabs`` (given by the caller, else new tensors of zeros) keep what they held."""
+    assert blocks.ndim == 3 and blocks.shape[1] == blocks.shape[2] and blocks.shape[1] >= 1
+    assert blocks.stride(2) == 1 and blocks.stride(1) == blocks.shape[1]
+    nb, m = int(blocks.shape[0]), int(blocks.shape[1])
+    stride = blocks.stride(0) if nb > 1 else m * m
+    if sign is None:
+        sign = torch.zeros(nb, dtype=torch.float64, device=blocks.device)
+    if logabs is None:
+        logabs = torch.zeros(nb, dtype=torch.float64, device=blocks.device)
+    assert sign.dtype == logabs.dtype == torch.float64 and sign.is_contiguous() and logabs.is_contiguous()
+    assert sign.numel() >= nb and logabs.numel() >= nb
+    if which is not None:
+        assert which.dtype == torch.int32 and which.is_contiguous() and which.numel() >= nb
+    device_for(blocks).slogdet_batch(_DT[blocks.dtype], _p(blocks), stride, m, nb,
+                                     0 if which is None else _p(which), _p(sign), _p(logabs))
+    return sign, logabs

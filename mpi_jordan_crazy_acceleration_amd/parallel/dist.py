@@ -141,7 +141,8 @@ class DistributedGaussJordan:
 
     def __init__(self, n: int, m: int, dtype: str = "fp64", chunk_cols: int = 0, eps: float = 1e-15,
                  sync_debug: bool = False, host_threads: int = 0, local_rank: Optional[int] = None,
-                 depth: int = 0, pivot: str = "block-min-inv-norm", comm_timeout: float = 600.0):
+                 depth: int = 0, pivot: str = "block-min-inv-norm", comm_timeout: float = 600.0,
+                 det: bool = False):
         C = load_native()
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised")
@@ -171,7 +172,7 @@ class DistributedGaussJordan:
         # comm_timeout: seconds any wait on a peer may take before every rank fails with the step,
         # phase and collective it was in (Engine::solve), instead of hanging
         self.engine = C.Engine(self.device, self.comm, self.n, self.m, dtype, chunk_cols, eps, sync_debug, depth,
-                               comm_timeout_s=float(comm_timeout), pivot=pivot)
+                               comm_timeout_s=float(comm_timeout), pivot=pivot, track_det=bool(det))
         self.layout = Layout(self.n, self.m, self.world, self.rank)
         self._rows = global_rows(self.n, self.m, self.world, self.rank)
 
@@ -251,6 +252,17 @@ class DistributedGaussJordan:
         if info["status"] != 0:
             raise RuntimeError(STATUS.get(info["status"], "error"))
         return {key: info[key] for key in ("k", "min_pivot", "cond1", "seconds")}
+
+    def slogdet(self):
+        """Collective, after solve() of a solver built with ``det=True``: (sign, log|det|) of the
+        matrix the resident inverse belongs to (Engine::slogdet; it follows every ``update``), the
+        same pair of Python floats on every rank."""
+        from ..models.gauss_jordan import STATUS
+
+        d = self.engine.slogdet()
+        if d["status"] != 0:
+            raise RuntimeError(STATUS.get(d["status"], "error") + ": slogdet needs det=True and a successful solve()")
+        return float(d["sign"]), float(d["logabsdet"])
 
     # ---- output
     def local_rows(self) -> np.ndarray:
