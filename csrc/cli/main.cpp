@@ -44,6 +44,11 @@
 //   --det                keep the pivot blocks' inverses and print "slogdet: <sign> <log|det|>" after
 //                        the residual line (Engine::slogdet; of A + U V^T after an update); --json
 //                        gains "slogdet": [sign, logabsdet]
+//   --equilibrate        scale A's rows and columns by powers of two ahead of the sweep and undo the
+//                        exponents on the inverse (SolveOptions::equilibrate): both singularity tests
+//                        become independent of the units of A's rows and columns.  stdout keeps its
+//                        form (the A corner is the matrix as given, the residual is against it);
+//                        --json gains "equilibrate": {applied, row_exp_range, col_exp_range}
 //   --json               machine-readable report on stderr
 //   --bcast auto|ring|direct  pivot-row broadcast algorithm at p > 2 (sets GJ_BCAST; auto = timed
 //                        against each other at startup, Comm::tune_bcast)
@@ -136,6 +141,15 @@ static void json_report(const RunConfig& cfg, const RunReport& rep) {
     };
     det = ", \"slogdet\": [" + num(rep.det.sign, "%.1f") + ", " + num(rep.det.logabsdet, "%.15e") + "]";
   }
+  if (cfg.solve.equilibrate) {
+    const SolveStats::Equil& q = rep.stats.equil;
+    char buf[160];
+    std::snprintf(buf, sizeof buf,
+                  ", \"equilibrate\": {\"applied\": %s, \"row_exp_range\": [%d, %d], \"col_exp_range\": [%d, %d]}",
+                  q.applied ? "true" : "false", (int)q.row_exp_min, (int)q.row_exp_max, (int)q.col_exp_min,
+                  (int)q.col_exp_max);
+    det += buf;
+  }
   std::fprintf(stderr,
                "{\"n\": %lld, \"m\": %lld, \"ranks\": %d, \"device\": \"%s\", \"comm\": \"%s\", "
                "\"dtype\": \"%s\", \"status\": %d, \"glob_time\": %.6f, \"best_time\": %.6f, "
@@ -220,6 +234,7 @@ int main(int argc, char* argv[]) {
       else if (a == "--refine") cfg.refine = std::atoi(val("--refine"));
       else if (a == "--json") json = true;
       else if (a == "--det") cfg.solve.track_det = true;
+      else if (a == "--equilibrate") cfg.solve.equilibrate = true;
       else if (a == "--bcast") {
         const std::string b = val("--bcast");
         if (b != "auto" && b != "ring" && b != "direct") return usage(argv[0]);

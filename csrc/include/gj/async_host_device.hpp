@@ -119,6 +119,11 @@ class AsyncHostDevice : public Device {
                    const double* Z, int64_t ldz, int64_t k, double sign, int s) override;
   void slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb, const int32_t* which,
                      double* sign, double* logabs, int s) override;
+  void abs_max_rows(DType dt, const void* X, int64_t ldx, const Layout& L, double* out_nat, int s) override;
+  void abs_max_cols(DType dt, const void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat, double* out,
+                    int s) override;
+  void scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat, const int32_t* cexp,
+                  int s) override;
 
   // A fence between queues: signalled by the stream that records it, waited on by any stream
   // (of any AsyncHostDevice of this process) or by the host.

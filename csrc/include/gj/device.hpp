@@ -10,6 +10,8 @@
 // Every op takes a stream role (S_MAIN/S_SIDE/S_COMM); the host device executes synchronously.
 #pragma once
 
+#include <cmath>
+#include <limits>
 #include <memory>
 #include <string>
 
@@ -493,7 +495,45 @@ class Device {
                              const int32_t* which, double* sign, double* logabs, int s) = 0;
   virtual size_t slogdet_scratch_bytes(int64_t m, int64_t nb) const { (void)m; (void)nb; return 0; }
   virtual void prepare_slogdet(int64_t m, int64_t nb) { (void)m; (void)nb; }
+
+  // ---- power-of-two equilibration of a panel (SolveOptions::equilibrate) ----
+  // X is this rank's rows of a panel, L.rows x L.npad of dtype dt, leading dimension ldx.  The three
+  // ops work on its real rows (global row grow(r) = ((r / m) * p + rank) * m + r % m below L.n) and
+  // its columns c < L.n.  Never read: X's padding rows, its columns >= n and every pitch gap, and the
+  // entries of a natural-order exponent vector that belong to other ranks' rows.
+  // Both maxima are taken in fp64 (an fp32 element is widened exactly) and a NaN or an Inf entry counts
+  // as +Inf, never NaN, so that Comm::allreduce_max over the ranks cannot lose it.  No floating-point
+  // atomics; the result does not depend on the grid (a maximum is exact in any order).
+  // GPU: rows are addressed with 64-bit offsets, so every leading dimension is accepted; the byte
+  // offsets inside a row are 32-bit, and an n whose row does not fit them is Status::BadArgs.
+  //
+  // out_nat[grow(r)] = max_{c<n} |X[r][c]| for this rank's real rows; other entries of out_nat
+  // (n doubles, natural row order) are left untouched.
+  virtual void abs_max_rows(DType dt, const void* X, int64_t ldx, const Layout& L, double* out_nat, int s) = 0;
+  // out[c] = max over this rank's real rows of ldexp(|X[r][c]|, rexp_nat[grow(r)]) for c < n: the
+  // column maxima of the row-scaled panel (LAPACK geequ's second pass).  rexp_nat: int32[n] in natural
+  // row order (device), null = all 0.  out is written, not accumulated: a rank without real rows
+  // writes +0.0.  A scaled value that overflows is +Inf.
+  virtual void abs_max_cols(DType dt, const void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat,
+                            double* out, int s) = 0;
+  // X[r][c] = round_dt(ldexp((double)X[r][c], rexp_nat[grow(r)] + cexp[c])) over the real rows and the
+  // columns c < n, in place.  rexp_nat as above, cexp: int32[n] (device), null = all 0.  Exact unless
+  // the result leaves dt's normal range: NaN, +-Inf and +-0 (with its sign) are kept, an underflow is
+  // rounded once (gradually, to a subnormal or a signed zero), an overflow gives +-Inf.  Nothing is
+  // written outside the real rows x n columns, so the padding identity of diag(A, I) survives bit for
+  // bit.
+  virtual void scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat,
+                          const int32_t* cexp, int s) = 0;
 };
+
+// The exponent rule of the equilibration, one place for the engine and every executor's tests: the e
+// with ldexp(amax, e) in [1, 2), i.e. 1 - frexp(amax).exponent; 0 for a maximum that is 0 or not finite.
+inline int32_t equil_exponent(double amax) {
+  if (!(amax > 0.0) || !(amax < std::numeric_limits<double>::infinity())) return 0;
+  int e = 0;
+  (void)std::frexp(amax, &e);
+  return (int32_t)(1 - e);
+}
 
 // Test probe of Device::panel_rhs, like g_last_gemm_kernel: "host" on the host executor,
 // "rhs<16|32|64>:<f64|f32>:<vec|scalar>:s<split>" on the GPU.
@@ -504,5 +544,7 @@ inline thread_local const char* g_last_rhs_t_kernel = "";
 inline thread_local const char* g_last_rank_update_kernel = "";
 // The same of Device::slogdet_batch: "host", or "sld:<lds|glob>:<f64|f32>".
 inline thread_local const char* g_last_slogdet_kernel = "";
+// The same of the three equilibration ops: "host", or "eq:<rmax|cmax|scale>:<f64|f32>:<vec|scalar>".
+inline thread_local const char* g_last_equil_kernel = "";
 
 }  // namespace gj

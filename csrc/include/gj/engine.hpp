@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gj/comm.hpp"
@@ -83,6 +84,18 @@ struct SolveOptions {
   // (m * m elements each, counted in the work space) by the chunk pass on COMM before Ht_ is reused.
   // Off (default): allocation, launches and results are exactly those of an engine without it.
   bool track_det = false;
+  // Power-of-two equilibration of A ahead of the sweep (LAPACK geequ's rule with the scale factors
+  // rounded to powers of two, so that scaling is exact): row exponents rexp[i] = 1 - frexp(max_j
+  // |A[i][j]|).exponent, then column exponents cexp[j] by the same rule from the column maxima of the
+  // row-scaled matrix (0 for a maximum that is 0 or not finite); the sweep inverts As = ldexp(A, rexp[i]
+  // + cexp[j]) and the result panel gets ldexp(Y[i][j], cexp[i] + rexp[j]): bit for bit inv(A) as the
+  // sweep on As gives it.  Both singularity tests (||.||_inf < eps and a scalar pivot below eps ||.||_inf)
+  // then see the scaled matrix, so they no longer depend on the units of A's rows and columns.  The
+  // maxima are taken from the input panel in the engine's dtype: an fp32 engine scales what survived the
+  // conversion to fp32.  When every exponent is 0 no scaling pass runs and the solve is bit-identical to
+  // one without the option.  Off (default): allocation, launches and results are exactly those of an
+  // engine without it.
+  bool equilibrate = false;
 };
 
 // Device time per phase (sum over the solve; phases on different streams overlap in time).
@@ -117,6 +130,12 @@ struct SolveStats {
   bool profiled = false;
   double phase_ms[kNumPhases] = {};   // SolveOptions::profile only
   int64_t phase_calls[kNumPhases] = {};
+  // SolveOptions::equilibrate: whether a scaling pass ran (some exponent != 0) and the exponent ranges
+  struct Equil {
+    bool enabled = false;
+    bool applied = false;
+    int32_t row_exp_min = 0, row_exp_max = 0, col_exp_min = 0, col_exp_max = 0;
+  } equil;
 };
 
 // Result of Engine::solve_rhs.
@@ -282,6 +301,12 @@ class Engine {
   // ||inv(A)||_inf of its result (collective): the scale of the normalised residual
   // ||A inv(A) - I|| / (||A|| ||inv(A)|| eps) that utils/metrics.py gates on.
   double input_norm_inf() const { return norm_a_; }
+  // SolveOptions::equilibrate: the row and column exponents of the last solve (n entries each, the same
+  // on every rank; empty without the option or before a solve)
+  std::pair<const std::vector<int32_t>&, const std::vector<int32_t>&> equil_exponents() const {
+    return {eq_rexp_h_, eq_cexp_h_};
+  }
+  bool equil_applied() const { return eq_applied_; }
   double result_norm_inf();
 
   int64_t real_local_rows() const;
@@ -463,6 +488,18 @@ class Engine {
   GemmExtra chain_sel_[2], defer_sel_[2];  // by panel parity; rsel_m == 0: panel without a split
   void deferred_updates(int64_t v, int stream);
   double norm_a_ = -1;
+  // ||.||_inf of the matrix the sweep works on (both singularity tests): norm_a_, or that of the
+  // equilibrated panel
+  double norm_sweep_ = -1;
+  // SolveOptions::equilibrate (allocated only with the option): the exponents in natural order on the
+  // device and on the host, the maxima scratch (n doubles), and the exact sum of all exponents
+  double equilibrate_input(SolveStats& st);  // scales X_, returns the scaled panel's ||.||_inf (collective)
+  int32_t* eq_rexp_ = nullptr;
+  int32_t* eq_cexp_ = nullptr;
+  double* eq_max_ = nullptr;
+  std::vector<int32_t> eq_rexp_h_, eq_cexp_h_;
+  bool eq_applied_ = false;
+  int64_t eq_exp_sum_ = 0;
   double local_norm_ = 0;           // this rank's ||X||_inf part, computed by generate()
   bool local_norm_valid_ = false;   // X unchanged since generate()
   bool step_events_ = false;  // GJ_STEP_EVENTS=1: SIDE records ev_edit_ / ev_pp_ after every step

@@ -97,6 +97,11 @@ class HostDevice : public Device {
                    const double* Z, int64_t ldz, int64_t k, double sign, int s) override;
   void slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb, const int32_t* which,
                      double* sign, double* logabs, int s) override;
+  void abs_max_rows(DType dt, const void* X, int64_t ldx, const Layout& L, double* out_nat, int s) override;
+  void abs_max_cols(DType dt, const void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat, double* out,
+                    int s) override;
+  void scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat, const int32_t* cexp,
+                  int s) override;
 
  private:
   int nthreads_ = 1;

@@ -254,6 +254,11 @@ class RaceCheckDevice : public Device {
                    const double* Z, int64_t ldz, int64_t k, double sign, int s) override;
   void slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb, const int32_t* which,
                      double* sign, double* logabs, int s) override;
+  void abs_max_rows(DType dt, const void* X, int64_t ldx, const Layout& L, double* out_nat, int s) override;
+  void abs_max_cols(DType dt, const void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat, double* out,
+                    int s) override;
+  void scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat, const int32_t* cexp,
+                  int s) override;
   size_t slogdet_scratch_bytes(int64_t m, int64_t nb) const override { return inner_->slogdet_scratch_bytes(m, nb); }
   void prepare_slogdet(int64_t m, int64_t nb) override { inner_->prepare_slogdet(m, nb); }
 

@@ -172,5 +172,19 @@ void slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int6
                    double* sign, double* logabs, void* scratch, hipStream_t s);
 const char* last_slogdet_kernel();
 
+// equilibrate.hip: Device::abs_max_rows / abs_max_cols / scale_pow2, one pass over X each.
+void abs_max_rows(DType dt, const void* X, int64_t ldx, const Layout& L, double* out_nat, hipStream_t s);
+void abs_max_cols(DType dt, const void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat, double* out,
+                  hipStream_t s);
+void scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat, const int32_t* cexp,
+                hipStream_t s);
+// Test hooks: row split of the following abs_max_cols launches (0 = auto, s >= 1 forces s; a launch never
+// runs an empty slice), the cache policy of scale_pow2's panel accesses (1 = non-temporal, the default;
+// 0 = plain, for measurements), and the name of this thread's last launch of the three,
+// "eq:<rmax|cmax|scale>:<f64|f32>:<vec|scalar>" ("host" on the host executor).
+void set_equil_col_split(int s);
+void set_equil_nt(int on);
+const char* last_equil_kernel();
+
 }  // namespace kern
 }  // namespace gj

@@ -112,9 +112,19 @@ PivotRule parse_pivot(const std::string& v) {
   throw std::invalid_argument("pivot: block-min-inv-norm | partial");
 }
 
+// SolveStats::equil as reports carry it: {applied, row_exp_range, col_exp_range}
+py::dict equil_to_dict(const SolveStats::Equil& q) {
+  py::dict d;
+  d["applied"] = q.applied;
+  d["row_exp_range"] = py::make_tuple(q.row_exp_min, q.row_exp_max);
+  d["col_exp_range"] = py::make_tuple(q.col_exp_min, q.col_exp_max);
+  return d;
+}
+
 py::dict stats_to_dict(const SolveStats& st) {
   py::dict d;
   d["status"] = (int)st.status;
+  if (st.equil.enabled) d["equilibrate"] = equil_to_dict(st.equil);
   d["singular_step"] = st.singular_step;
   d["seconds"] = st.seconds;
   d["host_wait_ms"] = st.host_wait_ms;
@@ -257,6 +267,13 @@ PYBIND11_MODULE(_C, mod) {
   mod.def("last_slogdet_kernel", [] { return std::string(kern::last_slogdet_kernel()); },
           "test probe: 'sld:<lds|glob>:<f64|f32>' of this thread's last Device.slogdet_batch ('host' on the "
           "host executor)");
+  mod.def("last_equil_kernel", [] { return std::string(kern::last_equil_kernel()); },
+          "test probe: 'eq:<rmax|cmax|scale>:<f64|f32>:<vec|scalar>' of this thread's last Device.abs_max_rows / "
+          "abs_max_cols / scale_pow2 ('host' on the host executor)");
+  mod.def("set_equil_col_split", [](int v) { kern::set_equil_col_split(v); },
+          "test hook: row split of the following Device.abs_max_cols launches on the GPU (0 = auto, s >= 1 forces s)");
+  mod.def("set_equil_nt", [](bool on) { kern::set_equil_nt(on ? 1 : 0); },
+          "Device.scale_pow2 on the GPU: panel accesses with the non-temporal policy (default) or plain (measurements)");
   mod.def("set_lat_glds", [](bool on) { kern::set_lat_glds(on ? 1 : 0); },
           "every latency GEMM of >= 1024 rows on the LDS-DMA kernel (tests; the engine sets it per launch)");
 
@@ -666,6 +683,48 @@ PYBIND11_MODULE(_C, mod) {
              d.col_abs_sum(parse_dtype(dt), (const void*)X, ldx, lay(n, m, p, k), (double*)out, S_MAIN);
              d.sync_stream(S_MAIN);
            })
+      // the equilibration ops (rexp_nat / cexp: int32 device arrays or 0)
+      .def("abs_max_rows",
+           [lay](Device& d, const std::string& dt, U X, int64_t ldx, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U out_nat) {
+             py::gil_scoped_release rel;
+             d.abs_max_rows(parse_dtype(dt), (const void*)X, ldx, lay(n, m, p, k), (double*)out_nat, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      .def("abs_max_cols",
+           [lay](Device& d, const std::string& dt, U X, int64_t ldx, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U rexp_nat, U out) {
+             py::gil_scoped_release rel;
+             d.abs_max_cols(parse_dtype(dt), (const void*)X, ldx, lay(n, m, p, k), (const int32_t*)rexp_nat,
+                            (double*)out, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      .def("scale_pow2",
+           [lay](Device& d, const std::string& dt, U X, int64_t ldx, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U rexp_nat, U cexp) {
+             py::gil_scoped_release rel;
+             d.scale_pow2(parse_dtype(dt), (void*)X, ldx, lay(n, m, p, k), (const int32_t*)rexp_nat,
+                          (const int32_t*)cexp, S_MAIN);
+             d.sync_stream(S_MAIN);
+           })
+      // device time per launch (microseconds) of the three equilibration ops: which = rmax | cmax | scale
+      // (scale alternates the sign of the exponents, so that X stays bounded)
+      .def("time_equil",
+           [lay](Device& d, const std::string& which, const std::string& dt, U X, int64_t ldx, int64_t n, int64_t m,
+                 U rexp, U cexp, U rexp_neg, U cexp_neg, U out, int reps) {
+             py::gil_scoped_release rel;
+             const Layout L = lay(n, m, 1, 0);
+             const DType t = parse_dtype(dt);
+             auto run = [&](int i) {
+               if (which == "rmax") d.abs_max_rows(t, (const void*)X, ldx, L, (double*)out, S_MAIN);
+               else if (which == "cmax") d.abs_max_cols(t, (const void*)X, ldx, L, (const int32_t*)rexp, (double*)out, S_MAIN);
+               else if (i % 2 == 0) d.scale_pow2(t, (void*)X, ldx, L, (const int32_t*)rexp, (const int32_t*)cexp, S_MAIN);
+               else d.scale_pow2(t, (void*)X, ldx, L, (const int32_t*)rexp_neg, (const int32_t*)cexp_neg, S_MAIN);
+             };
+             run(0);
+             run(1);
+             return time_launches(d, S_MAIN, reps, run);
+           })
       .def("gather_rows_natural",
            [lay](Device& d, U dst, int64_t ldd, U src, int64_t lds, int64_t n, int64_t m, int64_t p, int64_t ncols) {
              d.gather_rows_natural((double*)dst, ldd, (const double*)src, lds, lay(n, m, p, 0), ncols, S_MAIN);
@@ -841,9 +900,10 @@ PYBIND11_MODULE(_C, mod) {
       .def(py::init([](std::shared_ptr<Device> dev, std::shared_ptr<Comm> comm, int64_t n, int64_t m,
                        const std::string& dtype, int64_t chunk_cols, double eps, bool sync_debug,
                        int depth, bool profile, double comm_timeout_s, const std::string& pivot,
-                       double pivot_growth, bool track_det) {
+                       double pivot_growth, bool track_det, bool equilibrate) {
              SolveOptions o;
              o.track_det = track_det;
+             o.equilibrate = equilibrate;
              o.pivot_growth = pivot_growth;
              o.dtype = parse_dtype(dtype);
              o.depth = depth;
@@ -863,7 +923,20 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("chunk_cols") = 0, py::arg("eps") = kDefaultEps, py::arg("sync_debug") = false,
            py::arg("depth") = 0, py::arg("profile") = false, py::arg("comm_timeout_s") = 600.0,
            py::arg("pivot") = "block-min-inv-norm", py::arg("pivot_growth") = -1.0,
-           py::arg("track_det") = false)
+           py::arg("track_det") = false, py::arg("equilibrate") = false)
+      .def("equil_exponents",
+           [](PyEngine& e) -> py::object {
+             if (!e.eng->options().equilibrate) return py::none();
+             const auto rc = e.eng->equil_exponents();
+             const std::vector<int32_t>&r = rc.first, &c = rc.second;
+             py::dict d;
+             d["applied"] = e.eng->equil_applied();
+             d["row_exp"] = py::array_t<int32_t>((py::ssize_t)r.size(), r.data());
+             d["col_exp"] = py::array_t<int32_t>((py::ssize_t)c.size(), c.data());
+             return d;
+           },
+           "the last solve's equilibration {applied, row_exp, col_exp} (int32 arrays, the same on every rank); "
+           "None for an engine built without equilibrate=True")
       .def("slogdet",
            [](PyEngine& e) {
              DetResult dr;
@@ -1239,6 +1312,7 @@ PYBIND11_MODULE(_C, mod) {
     if (d.contains("refine_tol")) c.refine_tol = d["refine_tol"].cast<double>();
     if (d.contains("race_check")) c.race_check = d["race_check"].cast<bool>();
     if (d.contains("det")) c.solve.track_det = d["det"].cast<bool>();
+    if (d.contains("equilibrate")) c.solve.equilibrate = d["equilibrate"].cast<bool>();
     py::array_t<double, py::array::c_style | py::array::forcecast> inp;
     if (d.contains("input") && !d["input"].is_none()) {
       inp = d["input"].cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
@@ -1297,6 +1371,7 @@ PYBIND11_MODULE(_C, mod) {
       u["seconds"] = r.update.seconds;
       o["update"] = u;
     }
+    if (c.solve.equilibrate) o["equilibrate"] = equil_to_dict(r.stats.equil);
     if (r.det_computed) {
       o["slogdet"] = std::vector<double>{r.det.sign, r.det.logabsdet};
       o["slogdet_ranks"] = to_array(r.det_ranks, c.ranks, 2);

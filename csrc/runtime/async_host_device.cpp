@@ -380,4 +380,19 @@ void AsyncHostDevice::slogdet_batch(DType dt, const void* blocks, int64_t stride
   enqueue(s, [=] { inner_.slogdet_batch(dt, blocks, stride, m, nb, which, sign, logabs, s); });
 }
 
+void AsyncHostDevice::abs_max_rows(DType dt, const void* X, int64_t ldx, const Layout& L, double* out_nat, int s) {
+  g_last_equil_kernel = "host";
+  enqueue(s, [=] { inner_.abs_max_rows(dt, X, ldx, L, out_nat, s); });
+}
+void AsyncHostDevice::abs_max_cols(DType dt, const void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat,
+                                   double* out, int s) {
+  g_last_equil_kernel = "host";
+  enqueue(s, [=] { inner_.abs_max_cols(dt, X, ldx, L, rexp_nat, out, s); });
+}
+void AsyncHostDevice::scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat,
+                                 const int32_t* cexp, int s) {
+  g_last_equil_kernel = "host";
+  enqueue(s, [=] { inner_.scale_pow2(dt, X, ldx, L, rexp_nat, cexp, s); });
+}
+
 }  // namespace gj

@@ -459,4 +459,19 @@ void HipDevice::slogdet_batch(DType dt, const void* blocks, int64_t stride, int6
   check_launch();
 }
 
+void HipDevice::abs_max_rows(DType dt, const void* X, int64_t ldx, const Layout& L, double* out_nat, int s) {
+  kern::abs_max_rows(dt, X, ldx, L, out_nat, hs(streams_[s]));
+  check_launch();
+}
+void HipDevice::abs_max_cols(DType dt, const void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat,
+                             double* out, int s) {
+  kern::abs_max_cols(dt, X, ldx, L, rexp_nat, out, hs(streams_[s]));
+  check_launch();
+}
+void HipDevice::scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat,
+                           const int32_t* cexp, int s) {
+  kern::scale_pow2(dt, X, ldx, L, rexp_nat, cexp, hs(streams_[s]));
+  check_launch();
+}
+
 }  // namespace gj

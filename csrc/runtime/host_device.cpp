@@ -730,4 +730,56 @@ void HostDevice::slogdet_batch(DType dt, const void* blocks, int64_t stride, int
   });
 }
 
+// |x| as a key of the equilibration maxima: NaN and Inf count as +Inf
+static inline double equil_mag(double x) {
+  const double v = std::fabs(x);
+  return v < std::numeric_limits<double>::infinity() ? v : std::numeric_limits<double>::infinity();
+}
+
+void HostDevice::abs_max_rows(DType dt, const void* X, int64_t ldx, const Layout& L, double* out_nat, int) {
+  g_last_equil_kernel = "host";
+  parallel_for(L.rows, nthreads_, [&](int64_t r) {
+    const int64_t g = L.global_row(r);
+    if (g >= L.n) return;
+    double mx = 0.0;
+    for (int64_t c = 0; c < L.n; ++c)
+      mx = std::max(mx, equil_mag(dt == DType::F64 ? tp<double>(X)[r * ldx + c] : (double)tp<float>(X)[r * ldx + c]));
+    out_nat[g] = mx;
+  });
+}
+
+void HostDevice::abs_max_cols(DType dt, const void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat,
+                              double* out, int) {
+  g_last_equil_kernel = "host";
+  parallel_for(L.n, nthreads_, [&](int64_t c) {
+    double mx = 0.0;
+    for (int64_t r = 0; r < L.rows; ++r) {
+      const int64_t g = L.global_row(r);
+      if (g >= L.n) continue;
+      const double v = equil_mag(dt == DType::F64 ? tp<double>(X)[r * ldx + c] : (double)tp<float>(X)[r * ldx + c]);
+      mx = std::max(mx, std::ldexp(v, rexp_nat ? (int)rexp_nat[g] : 0));  // overflow: +Inf
+    }
+    out[c] = mx;
+  });
+}
+
+void HostDevice::scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat,
+                            const int32_t* cexp, int) {
+  g_last_equil_kernel = "host";
+  parallel_for(L.rows, nthreads_, [&](int64_t r) {
+    const int64_t g = L.global_row(r);
+    if (g >= L.n) return;
+    const int64_t re = rexp_nat ? (int64_t)rexp_nat[g] : 0;
+    for (int64_t c = 0; c < L.n; ++c) {
+      const int64_t e64 = re + (cexp ? (int64_t)cexp[c] : 0);
+      const int e = (int)std::max<int64_t>(-100000, std::min<int64_t>(100000, e64));  // (saturated either way)
+      // exact in fp64 for an fp32 element within any exponents an fp32 panel can produce; one rounding
+      if (dt == DType::F64)
+        tp<double>(X)[r * ldx + c] = std::ldexp(tp<double>(X)[r * ldx + c], e);
+      else
+        tp<float>(X)[r * ldx + c] = (float)std::ldexp((double)tp<float>(X)[r * ldx + c], e);
+    }
+  });
+}
+
 }  // namespace gj

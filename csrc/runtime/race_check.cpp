@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cstdio>
+#include <functional>
 #include <sstream>
 
 namespace gj {
@@ -843,6 +844,51 @@ void RaceCheckDevice::slogdet_batch(DType dt, const void* blocks, int64_t stride
   }
   check(s, "slogdet_batch", a);
   inner_->slogdet_batch(dt, blocks, stride, m, nb, which, sign, logabs, s);
+}
+
+// The equilibration ops: X's real rows x n columns (a prefix of the local rows), and of a natural-order
+// vector only the entries of the row blocks this rank owns.
+static void own_blocks(const Layout& L, const std::function<void(int64_t g0, int64_t h)>& f) {
+  for (int64_t b = 0; b < L.nblk; ++b) {
+    const int64_t g0 = L.global_block(b) * L.m, h = std::min<int64_t>(L.m, L.n - g0);
+    if (h > 0) f(g0, h);
+  }
+}
+void RaceCheckDevice::abs_max_rows(DType dt, const void* X, int64_t ldx, const Layout& L, double* out_nat, int s) {
+  std::vector<Acc> a;
+  const int64_t real = L.real_rows();
+  if (real > 0 && L.n > 0) {
+    a.push_back(R(rect(X, ldx, L.n, real, (int64_t)dtype_size(dt)), "X"));
+    own_blocks(L, [&](int64_t g0, int64_t h) { a.push_back(W(span(out_nat + g0, 8 * h), "out_nat")); });
+  }
+  check(s, "abs_max_rows", a);
+  inner_->abs_max_rows(dt, X, ldx, L, out_nat, s);
+}
+void RaceCheckDevice::abs_max_cols(DType dt, const void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat,
+                                   double* out, int s) {
+  std::vector<Acc> a;
+  const int64_t real = L.real_rows();
+  if (L.n > 0) {
+    if (real > 0) a.push_back(R(rect(X, ldx, L.n, real, (int64_t)dtype_size(dt)), "X"));
+    if (rexp_nat) own_blocks(L, [&](int64_t g0, int64_t h) { a.push_back(R(span(rexp_nat + g0, 4 * h), "rexp")); });
+    a.push_back(W(span(out, 8 * L.n), "out"));
+  }
+  check(s, "abs_max_cols", a);
+  inner_->abs_max_cols(dt, X, ldx, L, rexp_nat, out, s);
+}
+void RaceCheckDevice::scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat,
+                                 const int32_t* cexp, int s) {
+  std::vector<Acc> a;
+  const int64_t real = L.real_rows();
+  if (real > 0 && L.n > 0) {
+    if (rexp_nat) own_blocks(L, [&](int64_t g0, int64_t h) { a.push_back(R(span(rexp_nat + g0, 4 * h), "rexp")); });
+    if (cexp) a.push_back(R(span(cexp, 4 * L.n), "cexp"));
+    const auto x = rect(X, ldx, L.n, real, (int64_t)dtype_size(dt));
+    a.push_back(R(x, "X"));
+    a.push_back(W(x, "X"));
+  }
+  check(s, "scale_pow2", a);
+  inner_->scale_pow2(dt, X, ldx, L, rexp_nat, cexp, s);
 }
 
 }  // namespace gj

@@ -378,6 +378,8 @@ int Engine::alloc_buffers(std::string& why) {
   if (opt_.track_det)  // the H_t stash, slogdet_batch's selection, outputs and scratch: Nr is every rank's
     need_work += (size_t)L_.Nr * m * m * es + (size_t)L_.Nr * (2 * sizeof(double) + sizeof(int32_t)) +
                  kDetPart * sizeof(double) + dev_.slogdet_scratch_bytes(m, L_.Nr);
+  if (opt_.equilibrate)  // two exponent vectors and the maxima scratch
+    need_work += (size_t)std::max<int64_t>(L_.n, 1) * (2 * sizeof(int32_t) + sizeof(double));
   const size_t avail = dev_.on_gpu() ? dev_.free_memory() : SIZE_MAX;
   auto fits = [&](size_t need) { return !dev_.on_gpu() || need + (64u << 20) <= avail; };
   // stage 1: the matrix panels (the reference's a / b arrays)
@@ -448,6 +450,12 @@ void Engine::alloc_work(int64_t wmax) {
     det_out_ = static_cast<double*>(dev_.alloc(sizeof(double) * (2 * L_.Nr + kDetPart)));
     dev_.prepare_slogdet(m, L_.Nr);
   }
+  if (opt_.equilibrate) {
+    const size_t ne = (size_t)std::max<int64_t>(L_.n, 1);
+    eq_rexp_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * ne));
+    eq_cexp_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * ne));
+    eq_max_ = static_cast<double*>(dev_.alloc(sizeof(double) * ne));
+  }
   scores_ = static_cast<double*>(dev_.alloc(sizeof(double) * std::max<int64_t>(L_.nblk, 1)));
   valid_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * std::max<int64_t>(L_.nblk, 1)));
   pos_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * L_.Nr));
@@ -506,7 +514,8 @@ void Engine::label_work() {
       {valid_, "valid"}, {pos_, "pos"}, {phys_at_, "phys_at"}, {used_, "used"}, {seq_, "seq"}, {myrec_, "myrec"},
       {sel_done_, "sel_done"}, {recs_, "recs"}, {piv_dev_, "piv_dev"}, {dscratch_, "dscratch"},
       {iscratch_, "iscratch"}, {piv_host_, "piv_host"}, {ihost_, "ihost"}, {dhost_, "dhost"},
-      {vparts_, "vparts"}, {det_stash_, "det_stash"}, {det_which_, "det_which"}, {det_out_, "det_out"}};
+      {vparts_, "vparts"}, {det_stash_, "det_stash"}, {det_which_, "det_which"}, {det_out_, "det_out"},
+      {eq_rexp_, "eq_rexp"}, {eq_cexp_, "eq_cexp"}, {eq_max_, "eq_max"}};
   for (const auto& nv : named)
     if (nv.first) dev_.label(nv.first, nv.second);
 }
@@ -522,7 +531,9 @@ void Engine::free_work() {
                                reinterpret_cast<void**>(&recs_), reinterpret_cast<void**>(&piv_dev_),
                                reinterpret_cast<void**>(&dscratch_), reinterpret_cast<void**>(&iscratch_),
                                reinterpret_cast<void**>(&vparts_), &det_stash_,
-                               reinterpret_cast<void**>(&det_which_), reinterpret_cast<void**>(&det_out_)};
+                               reinterpret_cast<void**>(&det_which_), reinterpret_cast<void**>(&det_out_),
+                               reinterpret_cast<void**>(&eq_rexp_), reinterpret_cast<void**>(&eq_cexp_),
+                               reinterpret_cast<void**>(&eq_max_)};
   for (int i = 0; i < 3; ++i) dptrs.push_back(&At_[i]);
   for (int i = 0; i < 2; ++i) {
     dptrs.push_back(&Rb_[i]);
@@ -749,7 +760,7 @@ void Engine::select(int64_t t, const void* Lt, bool full) {
   const int par = hslot(t);
   // unused local blocks: exact at p = 1 (every step uses one), else counted as pivots arrive
   const int64_t nlive = L_.p == 1 ? L_.nblk - t : live_;
-  const double thresh = opt_.eps * norm_a_;
+  const double thresh = opt_.eps * norm_sweep_;
   Range rg(opt_.profile, "gj:select");
   int pe = prof_begin(S_SIDE);
   if (opt_.pivot == PivotRule::Partial && !full) {
@@ -1460,7 +1471,9 @@ SolveStats Engine::solve_steps() {
 
   norm_a_ = norm_inf();
   local_norm_valid_ = false;  // the sweep consumes X
-  if (std::fabs(norm_a_) < opt_.eps) {  // reference main.cpp:782 second clause
+  // the singularity tests see the matrix the sweep works on: A, or A equilibrated
+  norm_sweep_ = opt_.equilibrate ? equilibrate_input(st) : norm_a_;
+  if (std::fabs(norm_sweep_) < opt_.eps) {  // reference main.cpp:782 second clause
     st.status = Status::Singular;
     st.singular_step = 0;
     st.seconds = now_s() - t_begin;
@@ -1524,6 +1537,12 @@ SolveStats Engine::solve_steps() {
     cur_phase_ = "final exchange";
     const int pe = prof_begin(S_COMM);
     finalize(st.pivots);
+    if (eq_applied_) {
+      // inv(A)[i][j] = ldexp(Y[i][j], cexp[i] + rexp[j]): the exponents change sides.  finalize() has
+      // waited for the permutation (p = 1) or for the final exchange (COMM), so MAIN is ordered behind it.
+      dev_.scale_pow2(opt_.dtype, out_, npad, L_, eq_cexp_, eq_rexp_, S_MAIN);
+      comm_.drain(dev_, S_MAIN);
+    }
     prof_end(PH_FINALIZE, pe, S_COMM);
   }
   comm_.drain_all(dev_);
@@ -1541,6 +1560,50 @@ SolveStats Engine::solve_steps() {
     det_ready_ = true;
   }
   return st;
+}
+
+// ---------------------------------------------------------------- equilibration (SolveOptions::equilibrate)
+// Row maxima -> exponents -> column maxima of the row-scaled panel -> exponents -> one scaling pass, on
+// MAIN ahead of the sweep's first launch.  The maxima vectors are in natural order with 0 in the
+// entries of other ranks' rows, so one Comm::allreduce_max makes them global; every rank then derives
+// the same exponents from the same bits.
+double Engine::equilibrate_input(SolveStats& st) {
+  cur_phase_ = "equilibrate";
+  const int64_t n = L_.n;
+  const bool mine = real_local_rows() > 0;
+  std::vector<double> mx((size_t)n);
+  auto exponents = [&](std::vector<int32_t>& e, int32_t* dev_e, int32_t& lo, int32_t& hi) {
+    if (L_.p > 1) comm_.allreduce_max(dev_, eq_max_, (size_t)n, S_MAIN);
+    dev_.copy(mx.data(), eq_max_, sizeof(double) * (size_t)n, S_MAIN);
+    comm_.drain(dev_, S_MAIN);
+    e.resize((size_t)n);
+    bool any = false;
+    lo = hi = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      const int32_t v = equil_exponent(mx[(size_t)i]);
+      e[(size_t)i] = v;
+      any = any || v != 0;
+      lo = i == 0 ? v : std::min(lo, v);
+      hi = i == 0 ? v : std::max(hi, v);
+    }
+    dev_.copy(dev_e, e.data(), sizeof(int32_t) * (size_t)n, S_MAIN);
+    return any;
+  };
+  st.equil.enabled = true;
+  dev_.memset0(eq_max_, sizeof(double) * (size_t)n, S_MAIN);
+  if (mine) dev_.abs_max_rows(opt_.dtype, X_, L_.npad, L_, eq_max_, S_MAIN);
+  const bool any_r = exponents(eq_rexp_h_, eq_rexp_, st.equil.row_exp_min, st.equil.row_exp_max);
+  dev_.abs_max_cols(opt_.dtype, X_, L_.npad, L_, eq_rexp_, eq_max_, S_MAIN);
+  const bool any_c = exponents(eq_cexp_h_, eq_cexp_, st.equil.col_exp_min, st.equil.col_exp_max);
+  eq_applied_ = st.equil.applied = any_r || any_c;
+  eq_exp_sum_ = 0;
+  for (int64_t i = 0; i < n; ++i) eq_exp_sum_ += (int64_t)eq_rexp_h_[(size_t)i] + (int64_t)eq_cexp_h_[(size_t)i];
+  if (!eq_applied_) {  // nothing to scale: the solve is the one without the option
+    comm_.drain(dev_, S_MAIN);
+    return norm_a_;
+  }
+  if (mine) dev_.scale_pow2(opt_.dtype, X_, L_.npad, L_, eq_rexp_, eq_cexp_, S_MAIN);
+  return norm_inf();  // of the scaled panel (local_norm_valid_ is off)
 }
 
 // ---------------------------------------------------------------- det(A) from the pivot blocks
@@ -1594,6 +1657,9 @@ DetResult Engine::slogdet() {
   } else {
     out.sign = neg ? -1.0 : 1.0;
     out.logabsdet = part[0];
+    // the sweep inverted As = ldexp(A, rexp[i] + cexp[j]): det A = det As / 2^(sum of all exponents), a
+    // positive factor; the sum is exact and the same on every rank
+    if (eq_applied_) out.logabsdet -= 0.6931471805599453094 * (double)eq_exp_sum_;
   }
   out.seconds = now_s() - t0;
   det_ = out;

@@ -13,6 +13,9 @@ corner, ``residual: %e`` (or ``p == 1!`` with ``--residual compat`` on one rank)
 The in-process ``build/gj`` binary is the same contract with threads instead of processes.
 ``--det``: one more line after the residual line, ``slogdet: <sign> <logabsdet>`` (the determinant
 from the pivot blocks, ``DistributedGaussJordan.slogdet``), and ``"slogdet"`` in ``--json``.
+``--equilibrate``: power-of-two row and column scaling ahead of the sweep, undone on the inverse
+(``DistributedGaussJordan(equilibrate=True)``); stdout keeps its form (the A corner is the matrix as
+given, the residual is against it) and ``--json`` gains ``"equilibrate"``.
 ``--comm-timeout S``: a rank waiting longer than S seconds on a peer fails (every rank, naming the
 step, phase and collective).  ``--same-gpu``: rehearse the p-rank RCCL path with every rank on
 GPU 0 (each rank its own RCCL host over loopback sockets; functional check, not a timing).
@@ -68,6 +71,7 @@ def main(argv=None) -> int:
     ap.add_argument("--bcast", choices=["auto", "ring", "direct"], default=None)
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--det", action="store_true")
+    ap.add_argument("--equilibrate", action="store_true")
     ap.add_argument("--same-gpu", action="store_true")
     try:
         args, unknown = ap.parse_known_args(argv)
@@ -121,7 +125,7 @@ def main(argv=None) -> int:
             solver = DistributedGaussJordan(n, m, dtype=args.dtype, chunk_cols=args.chunk_cols, eps=args.eps,
                                             host_threads=args.host_threads, depth=args.depth, pivot=args.pivot,
                                             local_rank=local if gpu else None, comm_timeout=args.comm_timeout,
-                                            det=args.det)
+                                            det=args.det, equilibrate=args.equilibrate)
         except C.GJError as e:  # agreed on every rank inside the constructor
             out("Not enough memory!\n" if e.status == 2 else f"error: {e}\n")
             return 2
@@ -181,6 +185,8 @@ def main(argv=None) -> int:
                    "dtype": args.dtype, "status": st["status"], "glob_time": glob,
                    "gflops_nominal": 2.0 * n ** 3 / glob / 1e9 if glob > 0 else 0.0,
                    "residual": res, "offdiag_pivots": st["offdiag_pivots"]}
+            if "equilibrate" in st:
+                rec["equilibrate"] = {k: (list(v) if isinstance(v, tuple) else v) for k, v in st["equilibrate"].items()}
             if sld is not None:
                 rec["slogdet"] = [v if v - v == 0 else None for v in sld]  # JSON has no NaN or Infinity
             print(json.dumps(rec), file=sys.stderr, flush=True)

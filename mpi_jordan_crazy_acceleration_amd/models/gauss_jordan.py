@@ -52,6 +52,11 @@ class GaussJordan:
     host_threads: int = 0
     race_check: bool = False  # happens-before schedule checker (RaceCheckDevice): report["races"]
     det: bool = False  # keep the pivot blocks for Engine::slogdet (SolveOptions::track_det)
+    # Scale A's rows and columns by powers of two ahead of the sweep and undo the exponents on the inverse
+    # (SolveOptions::equilibrate): exact, and both singularity tests then ignore the units of A's rows and
+    # columns.  The exponents come from the engine's panel, so an fp32 engine scales what survived the
+    # conversion to fp32.  Off: nothing changes.
+    equilibrate: bool = False
     extra: dict = field(default_factory=dict)
 
     def _cfg(self, n: int) -> dict:
@@ -65,6 +70,8 @@ class GaussJordan:
                    race_check=bool(self.race_check))
         if self.det:
             cfg["det"] = True
+        if self.equilibrate:
+            cfg["equilibrate"] = True
         cfg.update(self.extra)
         return cfg
 
@@ -84,7 +91,8 @@ class GaussJordan:
         seconds}.
         ``det``: the report gains ``slogdet`` = [sign, logabsdet] of the matrix the inverse belongs to
         (Engine::slogdet; after the update, if one is given) and ``slogdet_ranks``, every rank's pair
-        (ranks x 2: the same bits in every row)."""
+        (ranks x 2: the same bits in every row).
+        With ``equilibrate`` the report gains ``equilibrate`` = {applied, row_exp_range, col_exp_range}."""
         cfg = self._cfg(n)
         if det:
             cfg["det"] = True
@@ -145,7 +153,8 @@ class GaussJordan:
         idx = a.device.index if a.device.index is not None else torch.cuda.current_device()
         eng = C.Engine(_hip_device(idx), C.self_comm(), n, int(self.block_size), self.dtype,
                        int(self.chunk_cols), float(self.eps), bool(self.sync_debug), int(self.depth),
-                       pivot=self.pivot, track_det=bool(track_det or self.det))
+                       pivot=self.pivot, track_det=bool(track_det or self.det),
+                       equilibrate=bool(self.equilibrate))
         torch.cuda.synchronize(a.device)  # A may have been written on torch's stream
         eng.upload_rows_device(a.data_ptr(), a.stride(0))
         st = eng.solve()
@@ -220,7 +229,9 @@ class Factored:
     lemma, one pass over the inverse instead of another inversion; ``updates`` counts the updates
     applied since the inversion and ``last_update`` holds the last one's result.
     ``slogdet()`` / ``det()``: the determinant of the matrix the handle stands for, from the pivot
-    blocks the inversion already computed (no second factorisation); they follow every ``update``."""
+    blocks the inversion already computed (no second factorisation); they follow every ``update``.
+    ``equilibration``: what ``equilibrate=True`` did to the inversion's input (None without it); the
+    inverse, the solves, the updates and the determinant all refer to A itself either way."""
 
     def __init__(self, gj: "GaussJordan", A):
         self._is_torch = isinstance(A, torch.Tensor)
@@ -246,13 +257,20 @@ class Factored:
         self._a64 = np.ascontiguousarray(a)
         self._eng = C.Engine(C.host_device(int(gj.host_threads)), C.self_comm(), self.n, int(gj.block_size),
                              gj.dtype, int(gj.chunk_cols), float(gj.eps), bool(gj.sync_debug), int(gj.depth),
-                             pivot=gj.pivot, track_det=True)
+                             pivot=gj.pivot, track_det=True, equilibrate=bool(gj.equilibrate))
         self._eng.upload_local_rows(self._a64)
         st = self._eng.solve()
         if st["status"] == 1:
             raise SingularMatrixError("singular matrix")
         if st["status"] != 0:
             raise RuntimeError(STATUS.get(st["status"], "error"))
+
+    @property
+    def equilibration(self) -> Optional[dict]:
+        """{"applied", "row_exp", "col_exp"} of the inversion (``equilibrate=True``): whether a scaling
+        pass ran and the int32 row / column exponents (numpy arrays of n), with As = ldexp(A, row_exp[i]
+        + col_exp[j]) the matrix the sweep inverted.  None when the option is off."""
+        return self._eng.equil_exponents()
 
     def solve(self, b, trans: bool = False, max_refine: int = -1, tol: float = 1e-15):
         if self._cuda:
@@ -421,7 +439,9 @@ def solve(A, b, block_size: int = 128, trans: bool = False, **kw):
 
 
 def run(n: int, m: int, ranks: int = 1, device: str = "auto", gen: str = "absdiff", seed: int = 0,
-        file: Optional[str] = None, dtype: str = "fp64", residual: str = "always", **kw) -> dict:
-    """The reference CLI flow in-process; returns the report dict (glob_time, residual, corners...)."""
+        file: Optional[str] = None, dtype: str = "fp64", residual: str = "always",
+        input: Optional[np.ndarray] = None, **kw) -> dict:
+    """The reference CLI flow in-process; returns the report dict (glob_time, residual, corners...).
+    ``input``: an n x n matrix instead of the generator or a file."""
     return GaussJordan(block_size=m, ranks=ranks, device=device, dtype=dtype, residual=residual,
-                       **kw).run(n, gen=gen, seed=seed, file=file)
+                       **kw).run(n, gen=gen, seed=seed, file=file, input=input)

@@ -307,6 +307,44 @@ def col_abs_sum(X: torch.Tensor, out: torch.Tensor, n: int, m: int, p: int = 1, 
     return out
 
 
+def _exp_ptr(e, n: int) -> int:
+    if e is None:
+        return 0
+    assert e.dtype == torch.int32 and e.stride(-1) == 1 and e.numel() >= n
+    return _p(e)
+
+
+def abs_max_rows(X: torch.Tensor, out_nat: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0) -> torch.Tensor:
+    """out_nat[grow(r)] = max_{c<n} |X[r, c]| for rank ``k``'s real local rows r (Device::abs_max_rows);
+    the other entries of ``out_nat`` (fp64, natural row order, >= n entries) stay untouched.  A NaN or an
+    Inf entry counts as +Inf.  ``X`` fp64 / fp32 with unit column stride; padding is never read."""
+    assert out_nat.dtype == torch.float64 and out_nat.stride(-1) == 1 and X.stride(-1) == 1
+    device_for(out_nat).abs_max_rows(_DT[X.dtype], _p(X), X.stride(0), n, m, p, k, _p(out_nat))
+    return out_nat
+
+
+def abs_max_cols(X: torch.Tensor, out: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0,
+                 rexp_nat: torch.Tensor = None) -> torch.Tensor:
+    """out[c] = max over rank ``k``'s real local rows of ldexp(|X[r, c]|, rexp_nat[grow(r)]) for c < n
+    (Device::abs_max_cols): the column maxima of the row-scaled panel, written (a rank without rows
+    writes +0.0), a NaN or an Inf entry counting as +Inf.  ``rexp_nat`` int32 in natural row order or
+    None (all 0); only this rank's rows' entries are read."""
+    assert out.dtype == torch.float64 and out.stride(-1) == 1 and X.stride(-1) == 1
+    device_for(out).abs_max_cols(_DT[X.dtype], _p(X), X.stride(0), n, m, p, k, _exp_ptr(rexp_nat, n), _p(out))
+    return out
+
+
+def scale_pow2(X: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0, rexp_nat: torch.Tensor = None,
+               cexp: torch.Tensor = None) -> torch.Tensor:
+    """X[r, c] = ldexp(X[r, c], rexp_nat[grow(r)] + cexp[c]) over rank ``k``'s real local rows and the
+    columns c < n, in place (Device::scale_pow2): exact unless the result leaves the dtype's normal
+    range (one rounding on underflow, +-Inf on overflow); NaN, +-Inf and +-0 are kept.  ``rexp_nat`` /
+    ``cexp`` int32 (natural row order / columns) or None (all 0).  Nothing else of X is written."""
+    assert X.stride(-1) == 1
+    device_for(X).scale_pow2(_DT[X.dtype], _p(X), X.stride(0), n, m, p, k, _exp_ptr(rexp_nat, n), _exp_ptr(cexp, n))
+    return X
+
+
 def slogdet_batch(blocks: torch.Tensor, which: torch.Tensor = None, sign: torch.Tensor = None,
                   logabs: torch.Tensor = None):
     """(sign, logabs) of the determinants of an (nb, m, m) batch (Device::slogdet_batch): an LU with

@@ -142,7 +142,7 @@ class DistributedGaussJordan:
     def __init__(self, n: int, m: int, dtype: str = "fp64", chunk_cols: int = 0, eps: float = 1e-15,
                  sync_debug: bool = False, host_threads: int = 0, local_rank: Optional[int] = None,
                  depth: int = 0, pivot: str = "block-min-inv-norm", comm_timeout: float = 600.0,
-                 det: bool = False):
+                 det: bool = False, equilibrate: bool = False):
         C = load_native()
         if not dist.is_initialized():
             raise RuntimeError("torch.distributed is not initialised")
@@ -172,7 +172,8 @@ class DistributedGaussJordan:
         # comm_timeout: seconds any wait on a peer may take before every rank fails with the step,
         # phase and collective it was in (Engine::solve), instead of hanging
         self.engine = C.Engine(self.device, self.comm, self.n, self.m, dtype, chunk_cols, eps, sync_debug, depth,
-                               comm_timeout_s=float(comm_timeout), pivot=pivot, track_det=bool(det))
+                               comm_timeout_s=float(comm_timeout), pivot=pivot, track_det=bool(det),
+                               equilibrate=bool(equilibrate))
         self.layout = Layout(self.n, self.m, self.world, self.rank)
         self._rows = global_rows(self.n, self.m, self.world, self.rank)
 
@@ -263,6 +264,12 @@ class DistributedGaussJordan:
         if d["status"] != 0:
             raise RuntimeError(STATUS.get(d["status"], "error") + ": slogdet needs det=True and a successful solve()")
         return float(d["sign"]), float(d["logabsdet"])
+
+    @property
+    def equilibration(self) -> Optional[dict]:
+        """After solve() of a solver built with ``equilibrate=True``: {"applied", "row_exp", "col_exp"}
+        (int32 arrays of n, the same on every rank; Engine::equil_exponents); None without the option."""
+        return self.engine.equil_exponents()
 
     # ---- output
     def local_rows(self) -> np.ndarray:
