@@ -156,6 +156,10 @@ class Device {
   virtual int device_index() const { return -1; }
 
   // ---- memory ----
+  // release and release_pinned return only after everything enqueued on the device has completed
+  // (hipFree and hipHostFree synchronise the device; the host executor is synchronous; the
+  // asynchronous one drains its queues; the schedule checker models a host sync), so memory may be
+  // released while work that uses it is still enqueued.  Owned through DevBuf (gj/buffer.hpp).
   virtual void* alloc(size_t bytes) = 0;
   virtual void release(void* p) = 0;
   virtual void* alloc_pinned(size_t bytes) = 0;

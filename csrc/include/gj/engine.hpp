@@ -33,6 +33,7 @@
 #include <utility>
 #include <vector>
 
+#include "gj/buffer.hpp"
 #include "gj/comm.hpp"
 #include "gj/device.hpp"
 
@@ -179,10 +180,71 @@ struct DetResult {
   double seconds = 0;            // this rank's wall time of the call (about 0 when the cached value is returned)
 };
 
-class Engine {
+// The engine's memory, each buffer an owning handle.  Engine derives from both structs, so the members
+// keep their names; as bases they are released after every other member of the engine has gone, and
+// Engine::free_work() / free_buffers() are whole-struct assignments from a fresh value.  A new buffer
+// is one member here and one statement in Engine::alloc_work().
+struct EnginePanels {
+  DevBuf<void> X_;    // input / working panel
+  DevBuf<void> out_;  // result panel
+};
+
+struct EngineWork {
+  static constexpr int kMaxDepth = GemmExtra::kMaxZeroRows;
+  // stacked K-major multipliers of a panel, (d*m) x rows, by panel index mod 3 (panel u's chunks
+  // read theirs while the look-ahead of panel u writes panel u+1's and SIDE edits them)
+  DevBuf<void> At_[3];
+  DevBuf<void> Rb_[2];   // stacked normalised pivot rows, chunk-major (d*m) x npad
+  DevBuf<void> PP_[2];   // panel pieces: R_t restricted to the panel's columns, (d*m) x (d*m)
+  // look-ahead rows: a panel's normalised pivot rows restricted to the NEXT panel's block columns,
+  // (q*m) x (qn*m), step-major; formed and broadcast ahead of the first chunk so that the next
+  // panel's look-ahead update (and with it the next pivot chain) does not wait for a whole chunk
+  DevBuf<void> LA_[2];
+  DevBuf<void> T2_;                    // LA temp when LA runs on SIDE, m x (d*m)
+  DevBuf<void> Lrow_[2][kMaxDepth];    // multipliers of pivot row s_t for earlier panel steps, K-major
+  DevBuf<void> Ht_[2][kMaxDepth];      // H_t^T
+  DevBuf<void> T_;                     // row-update temp, m x Wmax
+  DevBuf<void> RP_;                    // panel-piece temp, m x (d*m)
+  DevBuf<void> inv_;
+  // PivotRule::Partial: the chosen candidate (K-major m x m), its inverse, score / validity and a
+  // zero "used" flag
+  DevBuf<void> sel_;
+  DevBuf<void> inv1_;
+  DevBuf<double> score1_;
+  DevBuf<int32_t> valid1_;
+  DevBuf<int32_t> used1_;
+  DevBuf<double> scores_;
+  DevBuf<int32_t> valid_;
+  DevBuf<int32_t> pos_;
+  DevBuf<int32_t> phys_at_;
+  DevBuf<int32_t> used_;
+  DevBuf<int32_t> seq_;
+  DevBuf<PivotRec> myrec_;
+  DevBuf<int32_t> sel_done_;  // workgroup counter of the fused candidate-inverse + selection launch
+  DevBuf<PivotRec> recs_;
+  DevBuf<PivotResult> piv_dev_;
+  DevBuf<double> dscratch_;
+  DevBuf<uint64_t> vparts_;  // GJ_VERIFY: npanels x vslots x Device::kHashParts partial hashes
+  DevBuf<int32_t> iscratch_;
+  // SolveOptions::track_det: the H_t of every step (Nr blocks of m * m), slogdet_batch's selection and
+  // its 2 Nr outputs followed by Engine::kDetPart partial sums
+  DevBuf<void> det_stash_;
+  DevBuf<int32_t> det_which_;
+  DevBuf<double> det_out_;
+  // SolveOptions::equilibrate (allocated only with the option): the exponents in natural order and
+  // the maxima scratch (n doubles)
+  DevBuf<int32_t> eq_rexp_;
+  DevBuf<int32_t> eq_cexp_;
+  DevBuf<double> eq_max_;
+  // pinned host
+  DevBuf<PivotResult> piv_host_;
+  DevBuf<int32_t> ihost_;
+  DevBuf<double> dhost_;
+};
+
+class Engine : private EnginePanels, private EngineWork {
  public:
   Engine(Device& dev, Comm& comm, int64_t n, int64_t m, const SolveOptions& opt);
-  ~Engine();
   Engine(const Engine&) = delete;
   Engine& operator=(const Engine&) = delete;
 
@@ -339,7 +401,7 @@ class Engine {
   const std::string& bcast_algo() const { return bcast_algo_; }  // "ring" | "direct"
 
  private:
-  static constexpr int kMaxDepth = GemmExtra::kMaxZeroRows;
+  using EngineWork::kMaxDepth;
   // pinned pivot-result slots: one per step of a panel in flight (the host-free chain of one rank
   // enqueues a whole panel's steps before it reads any result)
   static constexpr int kPivSlots = 2 * kMaxDepth;
@@ -357,7 +419,6 @@ class Engine {
   int alloc_buffers(std::string& why);
   void alloc_work(int64_t wmax);
   void free_work();     // everything but the matrix panels
-  void label_work();    // buffer names for schedule-check reports
   void free_buffers();
   // Pivot search for step t on the multiplier segment Lt (SIDE stream); result -> piv_host_[hslot(t)].
   void select(int64_t t, const void* Lt, bool full = false);
@@ -444,6 +505,17 @@ class Engine {
 
   Device& dev_;
   Comm& comm_;
+  // What the device and the communicator keep on the engine's behalf goes with it, also when its own
+  // constructor throws: the communicator's reduction scratch (device memory of dev_) and the pointers
+  // to cur_step_ / cur_phase_ handed to Device::trace_context.
+  struct Detach {
+    Device& dev;
+    Comm& comm;
+    ~Detach() {
+      comm.free_scratch(dev);
+      dev.trace_context(nullptr, nullptr);
+    }
+  } detach_{dev_, comm_};
   SolveOptions opt_;
   Layout L_;
   int d_ = 1;
@@ -491,12 +563,9 @@ class Engine {
   // ||.||_inf of the matrix the sweep works on (both singularity tests): norm_a_, or that of the
   // equilibrated panel
   double norm_sweep_ = -1;
-  // SolveOptions::equilibrate (allocated only with the option): the exponents in natural order on the
-  // device and on the host, the maxima scratch (n doubles), and the exact sum of all exponents
+  // SolveOptions::equilibrate: the exponents in natural order on the host (on the device: EngineWork)
+  // and the exact sum of all exponents
   double equilibrate_input(SolveStats& st);  // scales X_, returns the scaled panel's ||.||_inf (collective)
-  int32_t* eq_rexp_ = nullptr;
-  int32_t* eq_cexp_ = nullptr;
-  double* eq_max_ = nullptr;
   std::vector<int32_t> eq_rexp_h_, eq_cexp_h_;
   bool eq_applied_ = false;
   int64_t eq_exp_sum_ = 0;
@@ -508,60 +577,15 @@ class Engine {
   std::vector<int64_t> cb0_, cb1_;
   std::vector<int64_t> chunk_of_;    // block -> chunk
 
-  // device buffers
-  void* X_ = nullptr;       // input / working panel
-  void* out_ = nullptr;     // result panel
-  // stacked K-major multipliers of a panel, (d*m) x rows, by panel index mod 3 (panel u's chunks
-  // read theirs while the look-ahead of panel u writes panel u+1's and SIDE edits them)
-  void* At_[3] = {nullptr, nullptr, nullptr};
-  void* Rb_[2] = {nullptr, nullptr};   // stacked normalised pivot rows, chunk-major (d*m) x npad
-  void* PP_[2] = {nullptr, nullptr};   // panel pieces: R_t restricted to the panel's columns, (d*m) x (d*m)
-  // look-ahead rows: a panel's normalised pivot rows restricted to the NEXT panel's block columns,
-  // (q*m) x (qn*m), step-major; formed and broadcast ahead of the first chunk so that the next
-  // panel's look-ahead update (and with it the next pivot chain) does not wait for a whole chunk
-  void* LA_[2] = {nullptr, nullptr};
-  void* T2_ = nullptr;                 // LA temp when LA runs on SIDE, m x (d*m)
-  void* Lrow_[2][kMaxDepth] = {};      // multipliers of pivot row s_t for earlier panel steps, K-major
-  void* Ht_[2][kMaxDepth] = {};        // H_t^T
-  void* T_ = nullptr;                  // row-update temp, m x Wmax
-  void* RP_ = nullptr;                 // panel-piece temp, m x (d*m)
-  void* inv_ = nullptr;
-  // PivotRule::Partial: the chosen candidate (K-major m x m), its inverse, score / validity, a zero
-  // "used" flag, and the one-block layout the inverse runs on
-  void* sel_ = nullptr;
-  void* inv1_ = nullptr;
-  double* score1_ = nullptr;
-  int32_t* valid1_ = nullptr;
-  int32_t* used1_ = nullptr;
+  // PivotRule::Partial: the one-block layout the chosen candidate's inverse runs on
   Layout L1_;
-  double* scores_ = nullptr;
-  int32_t* valid_ = nullptr;
-  int32_t* pos_ = nullptr;
-  int32_t* phys_at_ = nullptr;
-  int32_t* used_ = nullptr;
-  int32_t* seq_ = nullptr;
-  PivotRec* myrec_ = nullptr;
-  int32_t* sel_done_ = nullptr;  // workgroup counter of the fused candidate-inverse + selection launch
-  PivotRec* recs_ = nullptr;
-  PivotResult* piv_dev_ = nullptr;
-  double* dscratch_ = nullptr;
-  uint64_t* vparts_ = nullptr;  // GJ_VERIFY: npanels x vslots x Device::kHashParts partial hashes
-  int32_t* iscratch_ = nullptr;
-  // SolveOptions::track_det: the H_t of every step (Nr blocks of m * m), slogdet_batch's selection and
-  // its 2 Nr outputs followed by the kDetPart partial sums that go through the all-reduce; the last
-  // solve's pivots and the cached determinant
+  // SolveOptions::track_det: the kDetPart partial sums that go through the all-reduce follow
+  // slogdet_batch's 2 Nr outputs; the last solve's pivots and the cached determinant
   static constexpr int kDetPart = 3;
-  void* det_stash_ = nullptr;
-  int32_t* det_which_ = nullptr;
-  double* det_out_ = nullptr;
   std::vector<int32_t> det_pivots_;
   bool det_ready_ = false;   // the stash holds a finished solve's blocks
   bool det_cached_ = false;  // det_ is current
   DetResult det_;
-  // pinned host
-  PivotResult* piv_host_ = nullptr;
-  int32_t* ihost_ = nullptr;
-  double* dhost_ = nullptr;
   int64_t ihost_len_ = 0;
   PivotResult piv_[2][kMaxDepth];      // pivots of the panels in flight (by panel parity)
   int64_t live_ = 0;                   // local block rows not yet used as a pivot row (candidates)

@@ -400,14 +400,13 @@ PYBIND11_MODULE(_C, mod) {
       // as (step, found, phys, owner, logical, score), read after the stream completes)
       .def("pivot_global",
            [](Device& d, U recs, int p, int t, U pos, U phys_at, U used, U seq, U out) {
-             auto* h = static_cast<PivotResult*>(d.alloc_pinned_coherent(sizeof(PivotResult)));
+             const auto mirror = DevBuf<PivotResult>::pinned_coherent(d, 1);
+             PivotResult* h = mirror;
              h->step = -1;
              d.pivot_global((const PivotRec*)recs, (int32_t)p, (int32_t)t, (int32_t*)pos, (int32_t*)phys_at,
                             (int32_t*)used, (int32_t*)seq, (PivotResult*)out, h, S_MAIN);
              d.sync_stream(S_MAIN);
-             py::tuple r = py::make_tuple(h->step, h->found, h->phys, h->owner, h->logical, h->score);
-             d.release_pinned(h);
-             return r;
+             return py::make_tuple(h->step, h->found, h->phys, h->owner, h->logical, h->score);
            })
       // block_inverse with the selection run by the launch's last workgroup (PivotSelectArgs; `used`
       // doubles as used_w, as in Engine::select).  `done` is the caller's device counter (0 between
@@ -418,9 +417,10 @@ PYBIND11_MODULE(_C, mod) {
            [lay](Device& d, const std::string& dt, U Lt, int64_t ldl, U inv_t, U scores, U valid, U used,
                  int64_t n, int64_t m, int64_t p, int64_t k, double thresh, int64_t nlive, int t, U pos,
                  U phys_at, U seq, U rec, U out, U done) {
-             PivotResult* h = nullptr;
-             if (p == 1) {
-               h = static_cast<PivotResult*>(d.alloc_pinned_coherent(sizeof(PivotResult)));
+             DevBuf<PivotResult> pinned;
+             if (p == 1) pinned = DevBuf<PivotResult>::pinned_coherent(d, 1);
+             PivotResult* h = pinned;
+             if (h) {
                std::memset(h, 0, sizeof(PivotResult));
                h->step = -1;
              }
@@ -442,10 +442,7 @@ PYBIND11_MODULE(_C, mod) {
                                         S_MAIN);
              d.sync_stream(S_MAIN);
              py::object mirror = py::none();
-             if (h) {
-               mirror = py::make_tuple(h->step, h->found, h->phys, h->owner, h->logical, h->score);
-               d.release_pinned(h);
-             }
+             if (h) mirror = py::make_tuple(h->step, h->found, h->phys, h->owner, h->logical, h->score);
              return py::make_tuple(fused, mirror);
            },
            py::arg("dt"), py::arg("Lt"), py::arg("ldl"), py::arg("inv_t"), py::arg("scores"), py::arg("valid"),

@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "gj/buffer.hpp"
 #include "gj/comm.hpp"
 
 namespace gj {
@@ -156,7 +157,7 @@ std::string Comm::tune_bcast(Device& dev, std::vector<size_t> sizes) {
   const int p = size(), me = rank();
   const int s = S_COMM;
   const size_t maxb = sizes.back();
-  void* buf = dev.alloc(maxb);
+  const auto buf = DevBuf<void>::device(dev, maxb);
   // bit-exact delivery check of the direct path on BOTH communicators (COMM carries the row
   // segments, SIDE the panel pieces; root 1, so the root's own slice index is skipped)
   std::vector<uint32_t> pat(maxb / 4 + 1), got(maxb / 4 + 1);
@@ -227,7 +228,6 @@ std::string Comm::tune_bcast(Device& dev, std::vector<size_t> sizes) {
     wins_above = wins_above && win[i];
     if (wins_above) thr = sizes[i];
   }
-  dev.release(buf);
   direct_min_ = thr;
   for (size_t i = 0; i < sizes.size(); ++i) {
     char line[256];

@@ -7,6 +7,7 @@
 #include "gj/host_device.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <type_traits>
 #include <cmath>
 #include <cstdlib>
@@ -141,7 +142,14 @@ std::string HostDevice::describe() const {
   return "host(" + std::to_string(nthreads_) + " threads)";
 }
 
+// GJ_TEST_ALLOC_NTH=<n> (fault injection, tests only): the n-th allocation of the process fails.
 void* HostDevice::alloc(size_t bytes) {
+  static std::atomic<int64_t> count{0};
+  static const int64_t nth = [] {
+    const char* e = std::getenv("GJ_TEST_ALLOC_NTH");
+    return e ? std::atoll(e) : 0;
+  }();
+  if (++count == nth) throw Error(Status::NoMemory, "injected (GJ_TEST_ALLOC_NTH)");
   void* p = nullptr;
   if (posix_memalign(&p, 64, std::max<size_t>(bytes, 64)) != 0 || !p)
     throw Error(Status::NoMemory, "host allocation failed");

@@ -51,7 +51,8 @@ namespace {
 // `var`=<rank>:<tag>[,<rank>:<tag>...]: whether the list names (rank, tag).  Fault injection for
 // the failure-agreement tests:
 //   GJ_TEST_ALLOC_FAIL  tag = matrix | block | residual | residual_stream | residual64: that rank's
-//                       allocation of that stage fails;
+//                       allocation of that stage fails (GJ_TEST_ALLOC_NTH=<n>, HostDevice::alloc: the
+//                       n-th allocation of the process, whichever it is);
 //   GJ_TEST_HANG        tag = a step number: that rank never issues the pivot exchange of that
 //                       step (a rank stuck in, or dead before, a collective);
 //   GJ_TEST_CORRUPT     tag = a step number: that rank zeroes its copy of the step's normalised
@@ -205,7 +206,8 @@ Engine::Engine(Device& dev, Comm& comm, int64_t n, int64_t m, const SolveOptions
   comm_.set_timeout(opt_.comm_timeout_s);
   // Fault injection (tests only) must never pass for a normal run: every active knob is announced
   // on stderr once per engine and reported in the policy (bench.py / --json carry it).
-  for (const char* var : {"GJ_TEST_ALLOC_FAIL", "GJ_TEST_HANG", "GJ_TEST_CORRUPT", "GJ_TEST_DROP_WAIT"})
+  for (const char* var :
+       {"GJ_TEST_ALLOC_FAIL", "GJ_TEST_ALLOC_NTH", "GJ_TEST_HANG", "GJ_TEST_CORRUPT", "GJ_TEST_DROP_WAIT"})
     if (const char* e = std::getenv(var))
       if (*e) {
         if (!fault_injection_.empty()) fault_injection_ += " ";
@@ -243,6 +245,7 @@ Engine::Engine(Device& dev, Comm& comm, int64_t n, int64_t m, const SolveOptions
     free_work();
     block_mem_fail_ = true;
     block_mem_why_ = mine == 1 ? why : "not enough device memory for the work space on a peer rank";
+    std::fprintf(stderr, "gj: rank %d: no work space: %s\n", (int)L_.k, block_mem_why_.c_str());
   }
   // Broadcast algorithm for the panel pieces (m x d*m) and the pivot-row segments (m x chunk width):
   // ring or direct, measured here
@@ -331,12 +334,6 @@ Engine::Engine(Device& dev, Comm& comm, int64_t n, int64_t m, const SolveOptions
 
 }
 
-Engine::~Engine() {
-  free_buffers();
-  comm_.free_scratch(dev_);
-  dev_.trace_context(nullptr, nullptr);
-}
-
 Engine::Policy Engine::policy() const {
   Policy p;
   p.depth = d_;
@@ -388,10 +385,8 @@ int Engine::alloc_buffers(std::string& why) {
     if (!fits(need_matrix))
       throw Error(Status::NoMemory, "not enough device memory: the matrix panels need " +
                                         std::to_string(need_matrix) + " bytes, have " + std::to_string(avail));
-    X_ = dev_.alloc(panel);
-    out_ = dev_.alloc(panel);
-    dev_.label(X_, "X");
-    dev_.label(out_, "out");
+    X_ = DevBuf<void>::device(dev_, panel, "X");
+    out_ = DevBuf<void>::device(dev_, panel, "out");
   } catch (const Error& e) {
     if (e.status() != Status::NoMemory) throw;
     why = e.what();
@@ -418,66 +413,73 @@ int Engine::alloc_buffers(std::string& why) {
 void Engine::alloc_work(int64_t wmax) {
   const int64_t m = L_.m, rows = std::max<int64_t>(L_.rows, 1), npad = L_.npad, dm = (int64_t)d_ * m;
   const size_t es = esz();
-  for (int i = 0; i < 3; ++i) At_[i] = dev_.alloc((size_t)dm * rows * es);
+  const size_t nblk1 = (size_t)std::max<int64_t>(L_.nblk, 1);
+  using Raw = DevBuf<void>;
+  using I32 = DevBuf<int32_t>;
+  using F64 = DevBuf<double>;
+  // "At[1]", "Lrow[0][3]": the names schedule-check reports print
+  auto at = [](std::string name, int i, int j = -1) {
+    name += "[" + std::to_string(i) + "]";
+    return j < 0 ? name : name + "[" + std::to_string(j) + "]";
+  };
+  for (int i = 0; i < 3; ++i) At_[i] = Raw::device(dev_, (size_t)dm * rows * es, at("At", i).c_str());
   for (int i = 0; i < 2; ++i) {
-    Rb_[i] = dev_.alloc((size_t)dm * npad * es);
-    PP_[i] = dev_.alloc((size_t)dm * dm * es);
-    LA_[i] = dev_.alloc((size_t)dm * dm * es);
+    Rb_[i] = Raw::device(dev_, (size_t)dm * npad * es, at("Rb", i).c_str());
+    PP_[i] = Raw::device(dev_, (size_t)dm * dm * es, at("PP", i).c_str());
+    LA_[i] = Raw::device(dev_, (size_t)dm * dm * es, at("LA", i).c_str());
     for (int j = 0; j < d_; ++j) {
-      Lrow_[i][j] = dev_.alloc((size_t)std::max<int64_t>(j, 1) * m * m * es);
-      Ht_[i][j] = dev_.alloc((size_t)m * m * es);
+      Lrow_[i][j] = Raw::device(dev_, (size_t)std::max<int64_t>(j, 1) * m * m * es, at("Lrow", i, j).c_str());
+      Ht_[i][j] = Raw::device(dev_, (size_t)m * m * es, at("Ht", i, j).c_str());
     }
   }
-  T_ = dev_.alloc((size_t)m * wmax * es);
-  RP_ = dev_.alloc((size_t)m * dm * es);
-  T2_ = dev_.alloc((size_t)m * dm * es);
-  inv_ = dev_.alloc((size_t)std::max<int64_t>(L_.nblk, 1) * m * m * es);
+  T_ = Raw::device(dev_, (size_t)m * wmax * es, "T");
+  RP_ = Raw::device(dev_, (size_t)m * dm * es, "RP");
+  T2_ = Raw::device(dev_, (size_t)m * dm * es, "T2");
+  inv_ = Raw::device(dev_, nblk1 * m * m * es, "inv");
   if (opt_.pivot == PivotRule::Partial) {
     L1_ = Layout::make(m, m, 1, 0);
-    sel_ = dev_.alloc((size_t)m * m * es);
-    inv1_ = dev_.alloc((size_t)m * m * es);
-    score1_ = static_cast<double*>(dev_.alloc(sizeof(double)));
-    valid1_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t)));
-    used1_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t)));
+    sel_ = Raw::device(dev_, (size_t)m * m * es, "sel");
+    inv1_ = Raw::device(dev_, (size_t)m * m * es, "inv1");
+    score1_ = F64::device(dev_, 1);
+    valid1_ = I32::device(dev_, 1);
+    used1_ = I32::device(dev_, 1);
     dev_.memset0(used1_, sizeof(int32_t), S_SIDE);
     dev_.sync_stream(S_SIDE);
   }
   // the candidate-inverse kernel's scratch, now: not lazily inside the first timed pivot search
   dev_.prepare_block_inverse(opt_.dtype, L_, bi_hint_);
   if (opt_.track_det) {
-    det_stash_ = dev_.alloc((size_t)L_.Nr * m * m * es);
-    det_which_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * L_.Nr));
-    det_out_ = static_cast<double*>(dev_.alloc(sizeof(double) * (2 * L_.Nr + kDetPart)));
+    det_stash_ = Raw::device(dev_, (size_t)L_.Nr * m * m * es, "det_stash");
+    det_which_ = I32::device(dev_, (size_t)L_.Nr, "det_which");
+    det_out_ = F64::device(dev_, (size_t)(2 * L_.Nr + kDetPart), "det_out");
     dev_.prepare_slogdet(m, L_.Nr);
   }
   if (opt_.equilibrate) {
     const size_t ne = (size_t)std::max<int64_t>(L_.n, 1);
-    eq_rexp_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * ne));
-    eq_cexp_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * ne));
-    eq_max_ = static_cast<double*>(dev_.alloc(sizeof(double) * ne));
+    eq_rexp_ = I32::device(dev_, ne, "eq_rexp");
+    eq_cexp_ = I32::device(dev_, ne, "eq_cexp");
+    eq_max_ = F64::device(dev_, ne, "eq_max");
   }
-  scores_ = static_cast<double*>(dev_.alloc(sizeof(double) * std::max<int64_t>(L_.nblk, 1)));
-  valid_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * std::max<int64_t>(L_.nblk, 1)));
-  pos_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * L_.Nr));
-  phys_at_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * L_.Nr));
-  used_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * L_.Nr));
-  seq_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * L_.Nr));
-  myrec_ = static_cast<PivotRec*>(dev_.alloc(sizeof(PivotRec)));
-  sel_done_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t)));
+  scores_ = F64::device(dev_, nblk1, "scores");
+  valid_ = I32::device(dev_, nblk1, "valid");
+  pos_ = I32::device(dev_, (size_t)L_.Nr, "pos");
+  phys_at_ = I32::device(dev_, (size_t)L_.Nr, "phys_at");
+  used_ = I32::device(dev_, (size_t)L_.Nr, "used");
+  seq_ = I32::device(dev_, (size_t)L_.Nr, "seq");
+  myrec_ = DevBuf<PivotRec>::device(dev_, 1, "myrec");
+  sel_done_ = I32::device(dev_, 1, "sel_done");
   dev_.memset0(sel_done_, sizeof(int32_t), S_SIDE);
   dev_.sync_stream(S_SIDE);
-  recs_ = static_cast<PivotRec*>(dev_.alloc(sizeof(PivotRec) * L_.p));
-  piv_dev_ = static_cast<PivotResult*>(dev_.alloc(sizeof(PivotResult)));
-  dscratch_ = static_cast<double*>(dev_.alloc(sizeof(double) * 64));
+  recs_ = DevBuf<PivotRec>::device(dev_, (size_t)L_.p, "recs");
+  piv_dev_ = DevBuf<PivotResult>::device(dev_, 1, "piv_dev");
+  dscratch_ = F64::device(dev_, 64, "dscratch");
   if (opt_.verify)
-    vparts_ = static_cast<uint64_t*>(
-        dev_.alloc(sizeof(uint64_t) * Device::kHashParts * (size_t)npanels() * (size_t)vslots()));
+    vparts_ = DevBuf<uint64_t>::device(dev_, Device::kHashParts * (size_t)npanels() * (size_t)vslots(), "vparts");
   ihost_len_ = std::max<int64_t>(L_.Nr, 16) * 2 + 16;
-  iscratch_ = static_cast<int32_t*>(dev_.alloc(sizeof(int32_t) * ihost_len_));
-  piv_host_ = static_cast<PivotResult*>(dev_.alloc_pinned_coherent(sizeof(PivotResult) * kPivSlots));
-  ihost_ = static_cast<int32_t*>(dev_.alloc_pinned(sizeof(int32_t) * ihost_len_));
-  dhost_ = static_cast<double*>(dev_.alloc_pinned(sizeof(double) * 64));
-  label_work();
+  iscratch_ = I32::device(dev_, (size_t)ihost_len_, "iscratch");
+  piv_host_ = DevBuf<PivotResult>::pinned_coherent(dev_, kPivSlots, "piv_host");
+  ihost_ = I32::pinned(dev_, (size_t)ihost_len_, "ihost");
+  dhost_ = F64::pinned(dev_, 64, "dhost");
 
   if (ev_L_ >= 0) return;  // events are the device's; created once
   ev_L_ = dev_.create_event();
@@ -493,78 +495,11 @@ void Engine::alloc_work(int64_t wmax) {
   for (size_t c = 0; c < cb0_.size(); ++c) ev_c_.push_back(dev_.create_event());
 }
 
-// Buffer names in schedule-check reports (RaceCheckDevice).
-void Engine::label_work() {
-  static const char* at[3] = {"At[0]", "At[1]", "At[2]"};
-  static const char* rb[2] = {"Rb[0]", "Rb[1]"};
-  static const char* pp[2] = {"PP[0]", "PP[1]"};
-  static const char* la[2] = {"LA[0]", "LA[1]"};
-  for (int i = 0; i < 3; ++i) dev_.label(At_[i], at[i]);
-  for (int i = 0; i < 2; ++i) {
-    dev_.label(Rb_[i], rb[i]);
-    dev_.label(PP_[i], pp[i]);
-    dev_.label(LA_[i], la[i]);
-    for (int j = 0; j < d_; ++j) {
-      dev_.label(Lrow_[i][j], (std::string("Lrow[") + char('0' + i) + "][" + char('0' + j) + "]").c_str());
-      dev_.label(Ht_[i][j], (std::string("Ht[") + char('0' + i) + "][" + char('0' + j) + "]").c_str());
-    }
-  }
-  const std::pair<const void*, const char*> named[] = {
-      {T_, "T"}, {RP_, "RP"}, {T2_, "T2"}, {inv_, "inv"}, {sel_, "sel"}, {inv1_, "inv1"}, {scores_, "scores"},
-      {valid_, "valid"}, {pos_, "pos"}, {phys_at_, "phys_at"}, {used_, "used"}, {seq_, "seq"}, {myrec_, "myrec"},
-      {sel_done_, "sel_done"}, {recs_, "recs"}, {piv_dev_, "piv_dev"}, {dscratch_, "dscratch"},
-      {iscratch_, "iscratch"}, {piv_host_, "piv_host"}, {ihost_, "ihost"}, {dhost_, "dhost"},
-      {vparts_, "vparts"}, {det_stash_, "det_stash"}, {det_which_, "det_which"}, {det_out_, "det_out"},
-      {eq_rexp_, "eq_rexp"}, {eq_cexp_, "eq_cexp"}, {eq_max_, "eq_max"}};
-  for (const auto& nv : named)
-    if (nv.first) dev_.label(nv.first, nv.second);
-}
-
-void Engine::free_work() {
-  std::vector<void**> dptrs = {&T_, &T2_, &RP_, &inv_, &sel_, &inv1_, reinterpret_cast<void**>(&score1_),
-                               reinterpret_cast<void**>(&valid1_), reinterpret_cast<void**>(&used1_),
-                               reinterpret_cast<void**>(&scores_),
-                               reinterpret_cast<void**>(&valid_), reinterpret_cast<void**>(&pos_),
-                               reinterpret_cast<void**>(&phys_at_), reinterpret_cast<void**>(&used_),
-                               reinterpret_cast<void**>(&seq_), reinterpret_cast<void**>(&myrec_),
-                               reinterpret_cast<void**>(&sel_done_),
-                               reinterpret_cast<void**>(&recs_), reinterpret_cast<void**>(&piv_dev_),
-                               reinterpret_cast<void**>(&dscratch_), reinterpret_cast<void**>(&iscratch_),
-                               reinterpret_cast<void**>(&vparts_), &det_stash_,
-                               reinterpret_cast<void**>(&det_which_), reinterpret_cast<void**>(&det_out_),
-                               reinterpret_cast<void**>(&eq_rexp_), reinterpret_cast<void**>(&eq_cexp_),
-                               reinterpret_cast<void**>(&eq_max_)};
-  for (int i = 0; i < 3; ++i) dptrs.push_back(&At_[i]);
-  for (int i = 0; i < 2; ++i) {
-    dptrs.push_back(&Rb_[i]);
-    dptrs.push_back(&PP_[i]);
-    dptrs.push_back(&LA_[i]);
-    for (int j = 0; j < kMaxDepth; ++j) {
-      dptrs.push_back(&Lrow_[i][j]);
-      dptrs.push_back(&Ht_[i][j]);
-    }
-  }
-  for (void** p : dptrs)
-    if (*p) {
-      dev_.release(*p);
-      *p = nullptr;
-    }
-  std::vector<void**> hptrs = {reinterpret_cast<void**>(&piv_host_), reinterpret_cast<void**>(&ihost_),
-                               reinterpret_cast<void**>(&dhost_)};
-  for (void** p : hptrs)
-    if (*p) {
-      dev_.release_pinned(*p);
-      *p = nullptr;
-    }
-}
+void Engine::free_work() { static_cast<EngineWork&>(*this) = EngineWork(); }
 
 void Engine::free_buffers() {
   free_work();
-  for (void** p : {&X_, &out_})
-    if (*p) {
-      dev_.release(*p);
-      *p = nullptr;
-    }
+  static_cast<EnginePanels&>(*this) = EnginePanels();
 }
 
 void Engine::dbg_sync() {
@@ -1864,7 +1799,7 @@ void Engine::download_local_rows(double* host, int64_t ld) {
   if (real == 0) return;
   const size_t es = esz();
   const int64_t rows_per = std::max<int64_t>(1, (int64_t(128) << 20) / (n * (int64_t)es));
-  void* stage = dev_.alloc_pinned(std::min(rows_per, real) * n * es);
+  const auto stage = DevBuf<void>::pinned(dev_, std::min(rows_per, real) * n * es);
   for (int64_t r0 = 0; r0 < real; r0 += rows_per) {
     const int64_t nr = std::min(rows_per, real - r0);
     dev_.copy2d(stage, n * es, elem(out_, r0 * L_.npad), L_.npad * es, n * es, nr, S_MAIN);
@@ -1872,10 +1807,9 @@ void Engine::download_local_rows(double* host, int64_t ld) {
     for (int64_t r = 0; r < nr; ++r)
       for (int64_t j = 0; j < n; ++j)
         host[(r0 + r) * ld + j] = (opt_.dtype == DType::F64)
-                                      ? static_cast<double*>(stage)[r * n + j]
-                                      : (double)static_cast<float*>(stage)[r * n + j];
+                                      ? static_cast<double*>(stage.get())[r * n + j]
+                                      : (double)static_cast<float*>(stage.get())[r * n + j];
   }
-  dev_.release_pinned(stage);
 }
 
 std::vector<double> Engine::corner(int nm, int which) {
@@ -1883,7 +1817,7 @@ std::vector<double> Engine::corner(int nm, int which) {
   std::vector<double> mine((size_t)nm * nm + nm, 0.0);  // values + row mask
   void* src = (which == 0) ? X_ : out_;
   const size_t es = esz();
-  void* stage = dev_.alloc_pinned((size_t)nm * es + 16);
+  auto stage = DevBuf<void>::pinned(dev_, (size_t)nm * es + 16);
   for (int64_t b = 0; b < L_.nblk; ++b) {
     const int64_t g = L_.global_block(b);
     for (int64_t r = 0; r < m; ++r) {
@@ -1892,12 +1826,12 @@ std::vector<double> Engine::corner(int nm, int which) {
       dev_.copy(stage, elem(src, (b * m + r) * L_.npad), (size_t)nm * es, S_MAIN);
       dev_.sync_stream(S_MAIN);
       for (int j = 0; j < nm; ++j)
-        mine[gr * nm + j] = (opt_.dtype == DType::F64) ? static_cast<double*>(stage)[j]
-                                                       : (double)static_cast<float*>(stage)[j];
+        mine[gr * nm + j] = (opt_.dtype == DType::F64) ? static_cast<double*>(stage.get())[j]
+                                                       : (double)static_cast<float*>(stage.get())[j];
       mine[(size_t)nm * nm + gr] = 1.0;
     }
   }
-  dev_.release_pinned(stage);
+  stage.reset();
   const size_t sz = mine.size();
   std::vector<double> all(sz * L_.p);
   comm_.host_allgather(dev_, mine.data(), all.data(), sz * sizeof(double));
@@ -1935,7 +1869,7 @@ double Engine::residual_common(const void* A, bool wide) {
   const int64_t m = L_.m, p = L_.p, npad = L_.npad;
   const size_t es = esz();
   void* full = out_;
-  void* gath = nullptr;
+  DevBuf<void> gathered;  // p > 1: the whole inverse in natural row order
   if (p > 1) {
     const size_t per = (size_t)L_.max_nblk * m * npad * es;
     // the whole inverse on every rank: agree that it fits everywhere before the first allocation
@@ -1943,12 +1877,13 @@ double Engine::residual_common(const void* A, bool wide) {
     const bool fits = !injected_alloc_fail(L_.k, "residual") &&
                       (!dev_.on_gpu() || need + (64u << 20) <= dev_.free_memory());
     if (comm_.host_max(dev_, fits ? 0.0 : 1.0) > 0) return residual_streamed(A, wide);
-    full = dev_.alloc((size_t)npad * npad * es);
-    gath = dev_.alloc(per * p);
+    gathered = DevBuf<void>::device(dev_, (size_t)npad * npad * es);
+    full = gathered;
+    const auto gath = DevBuf<void>::device(dev_, per * p);
     void* send = out_;
-    void* tmp = nullptr;
+    DevBuf<void> tmp;
     if (L_.nblk < L_.max_nblk) {  // pad the send buffer to the common size
-      tmp = dev_.alloc(per);
+      tmp = DevBuf<void>::device(dev_, per);
       dev_.memset0(tmp, per, S_COMM);
       if (L_.nblk > 0) dev_.copy(tmp, out_, (size_t)L_.rows * npad * es, S_COMM);
       send = tmp;
@@ -1958,18 +1893,18 @@ double Engine::residual_common(const void* A, bool wide) {
       const int64_t nb = rows_owned(L_.Nr, p, q);
       for (int64_t j = 0; j < nb; ++j)
         dev_.copy(elem(full, (j * p + q) * m * npad),
-                  static_cast<char*>(gath) + q * per + (size_t)j * m * npad * es,
+                  static_cast<char*>(gath.get()) + q * per + (size_t)j * m * npad * es,
                   (size_t)m * npad * es, S_COMM);
     }
     comm_.drain(dev_, S_COMM);
-    if (tmp) dev_.release(tmp);
-    dev_.release(gath);
-  }
+  }  // tmp and gath go here, before the widened copy is allocated (residual_fp64_bytes)
   const DType rdt = wide ? DType::F64 : opt_.dtype;
   void* fullr = full;
+  DevBuf<double> widened;
   if (rdt != opt_.dtype) {  // widen the inverse (fp32 -> fp64)
-    fullr = dev_.alloc((size_t)npad * npad * 8);
-    dev_.widen(opt_.dtype, static_cast<double*>(fullr), npad, full, npad, npad, npad, S_MAIN);
+    widened = DevBuf<double>::device(dev_, (size_t)npad * npad);
+    fullr = widened;
+    dev_.widen(opt_.dtype, widened, npad, full, npad, npad, npad, S_MAIN);
   }
   double local = 0.0;
   if (L_.nblk > 0) {
@@ -1979,8 +1914,8 @@ double Engine::residual_common(const void* A, bool wide) {
     local = dhost_[0];
   }
   dev_.sync_stream(S_MAIN);
-  if (fullr != full) dev_.release(fullr);
-  if (p > 1) dev_.release(full);
+  widened.reset();
+  gathered.reset();
   last_residual_fp64_ = (rdt == DType::F64);
   return comm_.host_max(dev_, agreed_share(local));
 }
@@ -2003,9 +1938,9 @@ double Engine::residual_streamed(const void* A, bool wide) {
     throw Error(Status::NoMemory, "not enough device memory for the residual (" + std::to_string(need) +
                                       " bytes per rank even streamed)");
   const int s = S_COMM;  // the broadcasts' stream: every GEMM after its strip without a cross-stream hop
-  void* R = dev_.alloc((size_t)rows * npad * res);
-  void* S = dev_.alloc(per * es);
-  void* Sw = wide ? dev_.alloc(per * 8) : nullptr;
+  auto R = DevBuf<void>::device(dev_, (size_t)rows * npad * res);
+  auto S = DevBuf<void>::device(dev_, per * es);
+  auto Sw = wide ? DevBuf<double>::device(dev_, per) : DevBuf<double>();
   dev_.record(ev_main_, S_MAIN);  // A (MAIN) is complete before the first product
   dev_.wait(s, ev_main_);
   dev_.memset0(R, (size_t)rows * npad * res, s);
@@ -2016,7 +1951,7 @@ double Engine::residual_streamed(const void* A, bool wide) {
     comm_.bcast(dev_, buf, (size_t)nbq * m * npad * es, (int)q, s);
     const void* src = buf;
     if (wide) {
-      dev_.widen(opt_.dtype, static_cast<double*>(Sw), npad, buf, npad, nbq * m, npad, s);
+      dev_.widen(opt_.dtype, Sw, npad, buf, npad, nbq * m, npad, s);
       src = Sw;
     }
     if (L_.nblk > 0)
@@ -2032,9 +1967,9 @@ double Engine::residual_streamed(const void* A, bool wide) {
   }
   comm_.drain(dev_, s);
   if (L_.nblk > 0) local = dhost_[0];
-  dev_.release(R);
-  dev_.release(S);
-  if (Sw) dev_.release(Sw);
+  R.reset();
+  S.reset();
+  Sw.reset();
   last_residual_fp64_ = (rdt == DType::F64);
   return comm_.host_max(dev_, agreed_share(local));
 }
@@ -2042,17 +1977,9 @@ double Engine::residual_streamed(const void* A, bool wide) {
 double Engine::residual_generated(GenSpec g) {
   GJ_REQUIRE(solved_, "residual: solve() first");
   if (residual_wide()) {  // fp64 A straight from the generator
-    void* Aw = dev_.alloc((size_t)std::max<int64_t>(L_.rows, 1) * L_.npad * 8);
+    const auto Aw = DevBuf<double>::device(dev_, (size_t)std::max<int64_t>(L_.rows, 1) * L_.npad);
     dev_.generate(DType::F64, Aw, L_, g, S_MAIN);
-    double r = 0;
-    try {
-      r = residual_common(Aw, true);
-    } catch (...) {
-      dev_.release(Aw);
-      throw;
-    }
-    dev_.release(Aw);
-    return r;
+    return residual_common(Aw, true);
   }
   dev_.generate(opt_.dtype, X_, L_, g, S_MAIN);
   dev_.sync_stream(S_MAIN);
@@ -2070,7 +1997,7 @@ void Engine::upload_rows_into(void* P, DType dt, const double* host, int64_t ld)
   if (real > 0) {
     const int64_t rows_per = std::max<int64_t>(1, (int64_t(256) << 20) / (n * 8));
     const int64_t chunk = std::min(rows_per, real);
-    double* stage = static_cast<double*>(dev_.alloc(sizeof(double) * chunk * n));
+    const auto stage = DevBuf<double>::device(dev_, (size_t)(chunk * n));
     for (int64_t r0 = 0; r0 < real; r0 += chunk) {
       const int64_t nr = std::min(chunk, real - r0);
       dev_.copy2d(stage, n * 8, host + r0 * ld, ld * 8, n * 8, nr, S_MAIN);
@@ -2078,7 +2005,6 @@ void Engine::upload_rows_into(void* P, DType dt, const double* host, int64_t ld)
                           nr, n, S_MAIN);
       dev_.sync_stream(S_MAIN);
     }
-    dev_.release(stage);
   }
   dev_.sync_stream(S_MAIN);
 }
@@ -2086,17 +2012,9 @@ void Engine::upload_rows_into(void* P, DType dt, const double* host, int64_t ld)
 double Engine::residual_rows(const double* host, int64_t ld) {
   GJ_REQUIRE(solved_, "residual: solve() first");
   if (residual_wide()) {
-    void* Aw = dev_.alloc((size_t)std::max<int64_t>(L_.rows, 1) * L_.npad * 8);
-    double r = 0;
-    try {
-      upload_rows_into(Aw, DType::F64, host, ld);
-      r = residual_common(Aw, true);
-    } catch (...) {
-      dev_.release(Aw);
-      throw;
-    }
-    dev_.release(Aw);
-    return r;
+    const auto Aw = DevBuf<double>::device(dev_, (size_t)std::max<int64_t>(L_.rows, 1) * L_.npad);
+    upload_rows_into(Aw, DType::F64, host, ld);
+    return residual_common(Aw, true);
   }
   upload_local_rows(host, ld);
   solved_ = true;

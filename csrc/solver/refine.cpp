@@ -14,14 +14,13 @@ namespace gj {
 
 namespace {
 // full n-vector (double, host) -> padded device vector of the engine dtype
-void* upload_vector(Device& dev, DType dt, const double* v, int64_t n, int64_t npad) {
-  double* st = static_cast<double*>(dev.alloc(sizeof(double) * npad));
+DevBuf<void> upload_vector(Device& dev, DType dt, const double* v, int64_t n, int64_t npad) {
+  const auto st = DevBuf<double>::device(dev, (size_t)npad);
   dev.memset0(st, sizeof(double) * npad, S_MAIN);
   dev.copy(st, v, sizeof(double) * n, S_MAIN);
-  void* d = dev.alloc(dtype_size(dt) * npad);
+  auto d = DevBuf<void>::device(dev, dtype_size(dt) * npad);
   dev.upload_convert(dt, d, 1, st, 1, npad, 1, S_MAIN);
   dev.sync_stream(S_MAIN);
-  dev.release(st);
   return d;
 }
 
@@ -30,12 +29,11 @@ std::vector<double> local_matvec(Device& dev, DType dt, const void* P, const Lay
   const size_t es = dtype_size(dt);
   std::vector<double> y((size_t)L.rows, 0.0);
   if (L.rows == 0) return y;
-  void* yd = dev.alloc(es * L.rows);
+  const auto yd = DevBuf<void>::device(dev, es * L.rows);
   dev.gemm(dt, GemmOp::Store, ALayout::RowMajor, L.rows, 1, L.npad, P, L.npad, vd, 1, yd, 1, S_MAIN);
   std::vector<char> h(es * L.rows);
   dev.copy(h.data(), yd, es * L.rows, S_MAIN);
   dev.sync_stream(S_MAIN);
-  dev.release(yd);
   for (int64_t i = 0; i < L.rows; ++i)
     y[i] = dt == DType::F64 ? reinterpret_cast<double*>(h.data())[i] : (double)reinterpret_cast<float*>(h.data())[i];
   return y;
@@ -86,29 +84,20 @@ struct ColumnRule {
 // device / pinned buffers of one call, released together (after the device went idle)
 struct BufSet {
   Device& dev;
-  std::vector<void*> mem, pinned;
+  std::vector<DevBuf<void>> held;
+  DrainOnExit drain{dev};  // after `held`: runs before the buffers go
   explicit BufSet(Device& d) : dev(d) {}
   template <typename T>
   T* get(size_t count, bool zero = true) {
     const size_t bytes = sizeof(T) * std::max<size_t>(count, 1);
-    void* p = dev.alloc(bytes);
-    mem.push_back(p);
-    if (zero) dev.memset0(p, bytes, S_MAIN);
-    return static_cast<T*>(p);
+    held.push_back(DevBuf<void>::device(dev, bytes));
+    if (zero) dev.memset0(held.back(), bytes, S_MAIN);
+    return static_cast<T*>(held.back().get());
   }
   template <typename T>
   T* get_pinned(size_t count) {
-    void* p = dev.alloc_pinned(sizeof(T) * std::max<size_t>(count, 1));
-    pinned.push_back(p);
-    return static_cast<T*>(p);
-  }
-  ~BufSet() {
-    try {
-      dev.sync_all();
-    } catch (...) {
-    }
-    for (void* p : mem) dev.release(p);
-    for (void* p : pinned) dev.release_pinned(p);
+    held.push_back(DevBuf<void>::pinned(dev, sizeof(T) * std::max<size_t>(count, 1)));
+    return static_cast<T*>(held.back().get());
   }
 };
 }  // namespace
@@ -116,9 +105,7 @@ struct BufSet {
 void Engine::apply_inverse(const double* b, double* x) {
   GJ_REQUIRE(solved_, "apply_inverse: solve() first");
   const int64_t m = L_.m, n = L_.n, p = L_.p;
-  void* bd = upload_vector(dev_, opt_.dtype, b, n, L_.npad);
-  std::vector<double> mine = local_matvec(dev_, opt_.dtype, out_, L_, bd);
-  dev_.release(bd);
+  std::vector<double> mine = local_matvec(dev_, opt_.dtype, out_, L_, upload_vector(dev_, opt_.dtype, b, n, L_.npad));
   const int64_t per = L_.max_nblk * m;
   mine.resize((size_t)per, 0.0);
   std::vector<double> all((size_t)per * p);
@@ -133,9 +120,7 @@ void Engine::apply_inverse(const double* b, double* x) {
 
 double Engine::axb_residual(const double* x, const double* b) {
   const int64_t m = L_.m, n = L_.n;
-  void* xd = upload_vector(dev_, opt_.dtype, x, n, L_.npad);
-  std::vector<double> y = local_matvec(dev_, opt_.dtype, X_, L_, xd);
-  dev_.release(xd);
+  const std::vector<double> y = local_matvec(dev_, opt_.dtype, X_, L_, upload_vector(dev_, opt_.dtype, x, n, L_.npad));
   double local = 0.0;
   for (int64_t i = 0; i < L_.rows; ++i) {
     const int64_t gi = L_.global_block(i / m) * m + i % m;
@@ -188,56 +173,49 @@ RhsResult Engine::solve_rhs_impl(const double* b, double* x, const GenSpec* gen,
   GJ_REQUIRE(solved_, "solve_rhs: solve() first");
   const int64_t m = L_.m, n = L_.n;
   RhsResult rr;
-  double* Aw = static_cast<double*>(dev_.alloc((size_t)std::max<int64_t>(L_.rows, 1) * L_.npad * 8));
-  try {
-    stage_rows_f64(Aw, gen, host_rows, dev_rows, ld);
-    dev_.sync_stream(S_MAIN);
-    double bn = 0;
-    for (int64_t i = 0; i < n; ++i) bn = std::max(bn, std::fabs(b[i]));
-    if (bn == 0) bn = 1;
-    dev_.row_abs_max(DType::F64, Aw, L_.npad, L_, dscratch_, S_MAIN);  // ||A||_inf (fp64)
-    dev_.copy(dhost_, dscratch_, sizeof(double), S_MAIN);
-    dev_.sync_stream(S_MAIN);
-    const double an = comm_.host_max(dev_, L_.nblk > 0 ? dhost_[0] : 0.0);
-    apply_inverse(b, x);
-    std::vector<double> r((size_t)n), d((size_t)n);
-    std::vector<double> best_x(x, x + n);  // the iterate to return
-    ColumnRule rule;
-    for (int it = 0;; ++it) {
-      // r = b - A x (this rank's rows, fp64), all-gathered to the full vector
-      void* xd = upload_vector(dev_, DType::F64, x, n, L_.npad);
-      std::vector<double> y = local_matvec(dev_, DType::F64, Aw, L_, xd);
-      dev_.release(xd);
-      const int64_t per = L_.max_nblk * m;
-      std::vector<double> mine((size_t)per, 0.0), all((size_t)per * L_.p);
-      for (int64_t i = 0; i < L_.rows; ++i) {
-        const int64_t gi = L_.global_block(i / m) * m + i % m;
-        if (gi < n) mine[(size_t)i] = b[gi] - y[(size_t)i];
-      }
-      comm_.host_allgather(dev_, mine.data(), all.data(), sizeof(double) * per);
-      double rn = 0;
-      for (int64_t q = 0; q < L_.p; ++q)
-        for (int64_t j = 0; j < rows_owned(L_.Nr, L_.p, q); ++j)
-          for (int64_t e = 0; e < m; ++e) {
-            const int64_t gi = (j * L_.p + q) * m + e;
-            if (gi < n) {
-              r[(size_t)gi] = all[(size_t)q * per + j * m + e];
-              rn = std::max(rn, std::fabs(r[(size_t)gi]));
-            }
-          }
-      double xn = 0;
-      for (int64_t i = 0; i < n; ++i) xn = std::max(xn, std::fabs(x[i]));
-      if (rule.step(rr, it, rn, xn, an, bn, max_refine, tol)) best_x.assign(x, x + n);
-      if (!rule.active) break;
-      apply_inverse(r.data(), d.data());
-      for (int64_t i = 0; i < n; ++i) x[i] += d[(size_t)i];
+  const auto Aw = DevBuf<double>::device(dev_, (size_t)std::max<int64_t>(L_.rows, 1) * L_.npad);
+  stage_rows_f64(Aw, gen, host_rows, dev_rows, ld);
+  dev_.sync_stream(S_MAIN);
+  double bn = 0;
+  for (int64_t i = 0; i < n; ++i) bn = std::max(bn, std::fabs(b[i]));
+  if (bn == 0) bn = 1;
+  dev_.row_abs_max(DType::F64, Aw, L_.npad, L_, dscratch_, S_MAIN);  // ||A||_inf (fp64)
+  dev_.copy(dhost_, dscratch_, sizeof(double), S_MAIN);
+  dev_.sync_stream(S_MAIN);
+  const double an = comm_.host_max(dev_, L_.nblk > 0 ? dhost_[0] : 0.0);
+  apply_inverse(b, x);
+  std::vector<double> r((size_t)n), d((size_t)n);
+  std::vector<double> best_x(x, x + n);  // the iterate to return
+  ColumnRule rule;
+  for (int it = 0;; ++it) {
+    // r = b - A x (this rank's rows, fp64), all-gathered to the full vector
+    const std::vector<double> y =
+        local_matvec(dev_, DType::F64, Aw, L_, upload_vector(dev_, DType::F64, x, n, L_.npad));
+    const int64_t per = L_.max_nblk * m;
+    std::vector<double> mine((size_t)per, 0.0), all((size_t)per * L_.p);
+    for (int64_t i = 0; i < L_.rows; ++i) {
+      const int64_t gi = L_.global_block(i / m) * m + i % m;
+      if (gi < n) mine[(size_t)i] = b[gi] - y[(size_t)i];
     }
-    std::copy(best_x.begin(), best_x.end(), x);
-  } catch (...) {
-    dev_.release(Aw);
-    throw;
+    comm_.host_allgather(dev_, mine.data(), all.data(), sizeof(double) * per);
+    double rn = 0;
+    for (int64_t q = 0; q < L_.p; ++q)
+      for (int64_t j = 0; j < rows_owned(L_.Nr, L_.p, q); ++j)
+        for (int64_t e = 0; e < m; ++e) {
+          const int64_t gi = (j * L_.p + q) * m + e;
+          if (gi < n) {
+            r[(size_t)gi] = all[(size_t)q * per + j * m + e];
+            rn = std::max(rn, std::fabs(r[(size_t)gi]));
+          }
+        }
+    double xn = 0;
+    for (int64_t i = 0; i < n; ++i) xn = std::max(xn, std::fabs(x[i]));
+    if (rule.step(rr, it, rn, xn, an, bn, max_refine, tol)) best_x.assign(x, x + n);
+    if (!rule.active) break;
+    apply_inverse(r.data(), d.data());
+    for (int64_t i = 0; i < n; ++i) x[i] += d[(size_t)i];
   }
-  dev_.release(Aw);
+  std::copy(best_x.begin(), best_x.end(), x);
   return rr;
 }
 

@@ -258,6 +258,23 @@ def test_split_column_updates_bit_identical_on_gpu(p, comm, depth, monkeypatch, 
             gj.GaussJordan(block_size=m, ranks=p, device="gpu", comm=comm, depth=depth).inverse(A)
 
 
+@pytest.mark.gpu
+def test_constructor_throw_releases_device_memory(native, monkeypatch):
+    # the constructor refuses GJ_SPLIT=3 after both matrix panels and the work space were allocated
+    # (before any launch): what it held goes back, to the byte
+    n, m = 1024, 128
+    dev = native.hip_device(0)
+    eng = native.Engine(dev, native.self_comm(), n, m)  # (the device's own first-use allocations)
+    del eng
+    torch.cuda.synchronize()
+    before = torch.cuda.mem_get_info()[0]
+    monkeypatch.setenv("GJ_SPLIT", "3")
+    with pytest.raises(Exception, match="GJ_SPLIT"):
+        native.Engine(dev, native.self_comm(), n, m)
+    torch.cuda.synchronize()
+    assert torch.cuda.mem_get_info()[0] == before
+
+
 @pytest.mark.parametrize("p", [3, 8])
 def test_direct_bcast_loopback_ranks_on_one_gpu(p, monkeypatch):
     # the direct broadcast's grouped point-to-point rounds with device buffers, streams and events
