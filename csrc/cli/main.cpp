@@ -44,6 +44,14 @@
 //   --det                keep the pivot blocks' inverses and print "slogdet: <sign> <log|det|>" after
 //                        the residual line (Engine::slogdet; of A + U V^T after an update); --json
 //                        gains "slogdet": [sign, logabsdet]
+//   --bounds             with --rhs: the forward error bound and the componentwise backward error of
+//                        every column (Engine::solve_rhs_block with bounds; one right-hand side takes
+//                        the block path as one column).  stdout keeps its form; --json gains
+//                        "axb_ferr_cols" and "axb_berr_cols"
+//   --cond               print "cond: <kappa_1> <kappa_inf>" (||A||_p ||inv(A)||_p from the resident
+//                        inverse, Engine::cond; of A + U V^T after an update) after the residual line
+//                        and after the slogdet line when both are given; --json gains
+//                        "cond": {"one", "inf"}
 //   --equilibrate        scale A's rows and columns by powers of two ahead of the sweep and undo the
 //                        exponents on the inverse (SolveOptions::equilibrate): both singularity tests
 //                        become independent of the units of A's rows and columns.  stdout keeps its
@@ -108,6 +116,20 @@ static void json_report(const RunConfig& cfg, const RunReport& rep) {
     }
     rhs += "]";
     if (rep.trans) rhs += ", \"trans\": true";
+    if (rep.bounds) {  // --bounds: one entry per column, at any nrhs (JSON has no NaN or Infinity: null)
+      auto arr = [&](const char* name, auto&& item) {
+        rhs += std::string(", \"") + name + "\": [";
+        for (size_t j = 0; j < rep.rhs_cols.size(); ++j) {
+          char b[64];
+          const double v = item(rep.rhs_cols[j]);
+          std::snprintf(b, sizeof b, "%.6e", v);
+          rhs += (j ? ", " : "") + (std::isfinite(v) ? std::string(b) : std::string("null"));
+        }
+        rhs += "]";
+      };
+      arr("axb_ferr_cols", [](const RhsResult& c) { return c.ferr; });
+      arr("axb_berr_cols", [](const RhsResult& c) { return c.berr; });
+    }
     if (rep.nrhs > 1) {  // --nrhs K: one entry per column
       auto arr = [&](const char* name, auto&& item) {
         rhs += std::string(", \"") + name + "\": [";
@@ -140,6 +162,16 @@ static void json_report(const RunConfig& cfg, const RunReport& rep) {
       return std::string(b);
     };
     det = ", \"slogdet\": [" + num(rep.det.sign, "%.1f") + ", " + num(rep.det.logabsdet, "%.15e") + "]";
+  }
+  if (rep.cond_computed) {
+    auto num = [](double v) {
+      char b[64];
+      if (!std::isfinite(v)) return std::string("null");
+      std::snprintf(b, sizeof b, "%.15e", v);
+      return std::string(b);
+    };
+    det += ", \"cond\": {\"one\": " + num(rep.cond.a_norm1 * rep.cond.inv_norm1) + ", \"inf\": " +
+           num(rep.cond.a_norminf * rep.cond.inv_norminf) + "}";
   }
   if (cfg.solve.equilibrate) {
     const SolveStats::Equil& q = rep.stats.equil;
@@ -230,6 +262,8 @@ int main(int argc, char* argv[]) {
       else if (a == "--rhs") cfg.rhs = val("--rhs");
       else if (a == "--nrhs") cfg.nrhs = std::atoi(val("--nrhs"));
       else if (a == "--trans") cfg.trans = true;
+      else if (a == "--bounds") cfg.bounds = true;
+      else if (a == "--cond") cfg.cond = true;
       else if (a == "--out-x") x_file = val("--out-x");
       else if (a == "--refine") cfg.refine = std::atoi(val("--refine"));
       else if (a == "--json") json = true;
@@ -313,6 +347,8 @@ int main(int argc, char* argv[]) {
     if (std::isnan(rep.det.sign)) std::printf("slogdet: nan %.15e\n", rep.det.logabsdet);
     else std::printf("slogdet: %d %.15e\n", (int)rep.det.sign, rep.det.logabsdet);
   }
+  if (rep.cond_computed)  // only with --cond
+    std::printf("cond: %e %e\n", rep.cond.a_norm1 * rep.cond.inv_norm1, rep.cond.a_norminf * rep.cond.inv_norminf);
   if (rep.rhs_solved) {  // only with --rhs: the reference has no A x = b mode
     std::printf("solution x:\n");
     for (double v : rep.x_head) std::printf("%.2f\t", v);

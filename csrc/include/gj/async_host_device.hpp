@@ -115,6 +115,12 @@ class AsyncHostDevice : public Device {
   void axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S, int64_t lds,
                         double sign, int64_t rows, int64_t k, const int32_t* active, double* colmax, int s) override;
   void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) override;
+  void panel_abs_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+                     const double* C_in, int64_t ldc, double* Y, int64_t ldy, double* colmax, int s) override;
+  void panel_abs_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+                       double* S, int64_t lds, int s) override;
+  void bound_terms(const double* R, int64_t ldr, const double* D, int64_t ldd, double* G, int64_t ldg, int64_t rows,
+                   int64_t k, double nz_eps, double safe1, double safe2, double* berr, int s) override;
   void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw, bool w_natural,
                    const double* Z, int64_t ldz, int64_t k, double sign, int s) override;
   void slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb, const int32_t* which,

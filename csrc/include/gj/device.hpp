@@ -459,6 +459,41 @@ class Device {
   // dtype dt, leading dimension ldx; accumulated in fp64, NaN kept; padding never read.
   virtual void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) = 0;
 
+  // ---- error bounds of a refined solve (Engine::solve_rhs_block with bounds) ----
+  // The two products of panel_rhs / panel_rhs_t on absolute values, 1 <= k <= kMaxRhs columns (else
+  // Status::BadArgs), with their operands laid out as there.
+  // Both dtypes: fp64 throughout -- an fp32 element of P is widened exactly, V is not rounded, the
+  // products and their sum are fp64.  (The bounds' right-hand side is about u (|A| |x| + |b|), which
+  // leaves fp32's range for a small b.)  Every term is non-negative, so the result carries a relative
+  // error of at most gamma(terms + 2) in fp64 units.  A NaN or an Inf of P or V reaches every element
+  // it is a term of, also through a zero factor.  No floating-point atomics: the K / row split is
+  // summed in a fixed order, two launches on the same inputs give the same bits.
+  // GPU: a leading dimension ldp whose rows one tile cannot address with 32-bit byte offsets is
+  // refused with Status::BadArgs.
+  //
+  // Y[r][j] = |C_in[r][j]| + sum_{c<n} |P[r][c]| * |V[c][j]| for this rank's real local rows; the padded
+  // local rows of Y are written as |C_in| (or 0).  C_in: null = 0; may alias Y.  colmax (double[k],
+  // device, or null): colmax[j] = max |Y[r][j]| over the real rows, NaN kept.  Never read: what
+  // panel_rhs never reads (P's padding rows, its columns >= n, V's rows >= n, every pitch gap).
+  virtual void panel_abs_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                             int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy, double* colmax,
+                             int s) = 0;
+  // S[c][j] = sum_r |P[r][c]| * |V[grow(r)][j]| for c < L.n over this rank's real local rows: its term
+  // of |P_full|^T |V|, in natural order.  Rows >= n of S are not written.  Never read: what panel_rhs_t
+  // never reads (P's padding rows, its columns >= n, V's rows >= n and those of other ranks, every
+  // pitch gap).
+  virtual void panel_abs_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                               int64_t k, double* S, int64_t lds, int s) = 0;
+  // The elementwise step of LAPACK's xGERFS over rows x k fp64 elements, 1 <= k <= kMaxRhs (else
+  // Status::BadArgs): with R a residual and D = |A| |x| + |b| >= 0,
+  //   G[r][j]  = |R[r][j]| + nz_eps * D[r][j] (one fused multiply-add), plus safe1 where D[r][j] <= safe2
+  //   berr[j]  = max_r |R[r][j]| / D[r][j], with (|R| + safe1) / (D + safe1) where D[r][j] <= safe2
+  // the maximum with NaN kept as in row_abs_max.  berr (double[k], device) is written, not
+  // accumulated: +0.0 for rows == 0.  G may alias R.
+  virtual void bound_terms(const double* R, int64_t ldr, const double* D, int64_t ldd, double* G, int64_t ldg,
+                           int64_t rows, int64_t k, double nz_eps, double safe1, double safe2, double* berr,
+                           int s) = 0;
+
   // ---- the low-rank update of a resident panel (Engine::update_inverse) ----
   // X[r][c] = round_dt(X[r][c] + sign * sum_{j<k} W[wrow(r)][j] * Z[c][j]) for this rank's local rows r
   // whose global row grow(r) = ((r / m) * p + rank) * m + r % m is below L.n, and the columns c < L.n;
@@ -544,6 +579,9 @@ inline int32_t equil_exponent(double amax) {
 inline thread_local const char* g_last_rhs_kernel = "";
 // The same of Device::panel_rhs_t: "host", or "rhst<16|32|64>:<f64|f32>:<vec|scalar>:s<split>".
 inline thread_local const char* g_last_rhs_t_kernel = "";
+// The same of Device::panel_abs_rhs / panel_abs_rhs_t: "host", or
+// "abs<16|32|64>:<f64|f32>:<vec|scalar>:s<split>" / "abst..." for the transposed op.
+inline thread_local const char* g_last_abs_kernel = "";
 // The same of Device::rank_update: "host", or "rku<k padded to 4>:<f64|f32>:<vec|scalar>".
 inline thread_local const char* g_last_rank_update_kernel = "";
 // The same of Device::slogdet_batch: "host", or "sld:<lds|glob>:<f64|f32>".

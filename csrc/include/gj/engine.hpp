@@ -28,6 +28,7 @@
 #pragma once
 
 #include <algorithm>
+#include <limits>
 #include <memory>
 #include <string>
 #include <utility>
@@ -146,6 +147,22 @@ struct RhsResult {
   std::vector<double> history;   // ||b - A x_k||_inf / ||b||_inf for k = 0 (x = X b), 1, ...
   int steps = 0;                 // refinement steps applied
   bool converged = false;        // backward error <= tol
+  // Error bounds of the returned x (solve_rhs_block with bounds; NaN when not asked for), LAPACK's
+  // xGERFS quantities with the resident |inv(A)| in place of the xLACN2 estimate:
+  //   berr  the componentwise backward error max_i |r_i| / (|A| |x| + |b|)_i, r = b - A x in fp64
+  //   ferr  max_i (|inv(A)| (|r| + (n + 1) u (|A| |x| + |b|)))_i / ||x||_inf with u = 2^-53 (the
+  //         numerator alone when ||x||_inf == 0): a bound of ||x_true - x||_inf / ||x||_inf, to first
+  //         order in ||I - inv(A)_computed A|| as in LAPACK -- hence to be trusted when `converged` is
+  //         true; it is reported for every column, converged or not.
+  // For trans the same with A^T and inv(A)^T.
+  double ferr = std::numeric_limits<double>::quiet_NaN();
+  double berr = std::numeric_limits<double>::quiet_NaN();
+};
+
+// Result of Engine::cond: the 1- and inf-norms of A (from the rows the caller gives, in fp64) and of
+// the resident inverse (engine dtype, summed in fp64).  kappa_p = a_norm<p> * inv_norm<p>.
+struct CondResult {
+  double a_norm1 = 0, a_norminf = 0, inv_norm1 = 0, inv_norminf = 0;
 };
 
 // Result of Engine::solve_rhs_block: one RhsResult per column, the residual sweeps of the longest
@@ -322,13 +339,25 @@ class Engine : private EnginePanels, private EngineWork {
   // summed over the ranks by Comm::allreduce_sum (the same bits on every rank, already in natural
   // row order: no all-gather, no row reorder) and applied by Device::axpy_cols_masked.  The column
   // rule is the same; the backward error uses ||A^T||_inf = ||A||_1 (Device::col_abs_sum).
+  // bounds: after a group's columns have stopped, RhsResult::ferr / berr of every column's returned
+  // iterate (see RhsResult): D = |A| |x| + |b| and F = |inv(A)| G by Device::panel_abs_rhs (trans:
+  // panel_abs_rhs_t + allreduce_sum) in fp64 whatever the engine dtype, G and berr by
+  // Device::bound_terms with nz_eps = (n + 1) 2^-53, safe1 = (n + 1) DBL_MIN, safe2 = safe1 / 2^-53;
+  // r = b - A x is the loop's own residual where it belongs to the returned iterate, else recomputed.
+  // About one more sweep per group; x and the rest of the report do not depend on it.
   RhsBlockResult solve_rhs_block(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                  const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
-                                 int64_t ld, int max_refine, double tol, bool trans = false);
+                                 int64_t ld, int max_refine, double tol, bool trans = false, bool bounds = false);
   // The same with B and X in device memory (fp64), e.g. torch CUDA tensors.
   RhsBlockResult solve_rhs_block_device(const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx, int64_t k,
                                         const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
-                                        int64_t ld, int max_refine, double tol, bool trans = false);
+                                        int64_t ld, int max_refine, double tol, bool trans = false,
+                                        bool bounds = false);
+  // The norms behind the condition numbers kappa_1 and kappa_inf of the matrix the result panel
+  // inverts (after solve(); collective).  A as in solve_rhs_block (gen / host_rows / dev_rows_f64,
+  // staged once in fp64); Device::row_abs_max and col_abs_sum over A's rows and over the result panel,
+  // the column sums added over the ranks (Comm::allreduce_sum), the maxima taken with NaN kept.
+  CondResult cond(const GenSpec* gen, const double* host_rows, const void* dev_rows_f64, int64_t ld);
   // Low-rank update of the resident inverse (after solve()): the result panel becomes
   // inv(A + U V^T) = X - (X U) inv(C) (V^T X), C = I_k + V^T X U, X = inv(A), by one pass over X and
   // O(n^2 k) flops instead of another inversion.  Collective.  U and V are n x k, row-major (ldu,
@@ -443,7 +472,8 @@ class Engine : private EnginePanels, private EngineWork {
   void block_path_trans(BlockPath& f, const double* Aw, int64_t kw);
   RhsBlockResult solve_rhs_block_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                       bool on_device, const GenSpec* gen, const double* host_rows,
-                                      const void* dev_rows, int64_t ld, int max_refine, double tol, bool trans);
+                                      const void* dev_rows, int64_t ld, int max_refine, double tol, bool trans,
+                                      bool bounds);
   // This rank's rows of A in fp64 (ld npad) from the generator, an fp64 device array or host rows;
   // enqueued on MAIN, not waited for.
   void stage_rows_f64(double* Aw, const GenSpec* gen, const double* host_rows, const void* dev_rows, int64_t ld);

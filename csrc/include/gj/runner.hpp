@@ -41,6 +41,12 @@ struct RunConfig {
   // A^T x = b from the same inverse (Engine::solve_rhs_block with trans, at any nrhs >= 1); the
   // reported residual is then ||A^T x - b||_inf
   bool trans = false;
+  // With rhs / rhs_input: the error bounds of every column (Engine::solve_rhs_block with bounds, the
+  // block path at any nrhs >= 1), RhsResult::ferr / berr of RunReport::rhs_cols
+  bool bounds = false;
+  // ||A||_p ||inv(A)||_p for p = 1 and inf (Engine::cond) of the matrix the inverse belongs to, after
+  // the update if one is given
+  bool cond = false;
   // A low-rank update after the inversion (Engine::update_inverse): caller-owned n x update_k
   // row-major U and V, or null.  The inverse becomes that of A + U V^T, and the right-hand-side
   // solve, the residual and keep_inverse then refer to A + U V^T (every rank forms its fp64 rows of
@@ -86,6 +92,9 @@ struct RunReport {
   // history of the column with the largest residual, x_head the head of column 0
   int nrhs = 1;
   bool trans = false;               // the right-hand sides were solved against A^T
+  bool bounds = false;              // rhs_cols carry ferr / berr
+  bool cond_computed = false;       // RunConfig::cond: rank 0's norms
+  CondResult cond;
   std::vector<RhsResult> rhs_cols;
   bool updated = false;             // RunConfig::update_u / update_v were applied
   UpdateResult update;              // rank 0's result of it

@@ -158,6 +158,20 @@ void col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* 
 void set_rhs_t_split(int s);
 const char* last_rhs_t_kernel();
 
+// panel_abs.hip: Device::panel_abs_rhs / panel_abs_rhs_t / bound_terms.  The two products take the
+// split plans, the scratch sizes (panel_rhs_scratch_bytes / panel_rhs_t_scratch_bytes) and the test
+// hooks (set_rhs_splitk / set_rhs_t_split) of their siblings above.  Test probe: the name of this
+// thread's last launch of either, "abs<16|32|64>:<f64|f32>:<vec|scalar>:s<split>" or "abst..." for the
+// transposed one ("host" on the host executors).
+void panel_abs_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+                   const double* C_in, int64_t ldc, double* Y, int64_t ldy, double* colmax, void* scratch,
+                   hipStream_t s);
+void panel_abs_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+                     double* S, int64_t lds, void* scratch, hipStream_t s);
+void bound_terms(const double* R, int64_t ldr, const double* D, int64_t ldd, double* G, int64_t ldg, int64_t rows,
+                 int64_t k, double nz_eps, double safe1, double safe2, double* berr, hipStream_t s);
+const char* last_abs_kernel();
+
 // rank_update.hip: Device::rank_update, one pass over X.  Test probe: the name of this thread's last
 // launch, "rku<k padded to 4>:<f64|f32>:<vec|scalar>" ("host" on the host executor).
 void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw, bool w_natural,

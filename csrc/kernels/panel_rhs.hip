@@ -34,12 +34,6 @@ namespace kern {
 
 namespace {
 
-constexpr int kRhsMI = 2;                             // 16-row fragments per wave
-constexpr int kRhsWaves = 4;                          // waves per workgroup
-constexpr int kRhsTileM = 16 * kRhsMI * kRhsWaves;    // 128 rows per workgroup
-constexpr int kRhsKC = 32;                            // rows of V per LDS stage
-constexpr int kRhsMaxSplit = 64;
-
 // LDS row padding of V (elements): the 4 K lanes of a B-fragment read sit W rows apart; W * pitch =
 // 128 (mod 256) bytes in fp64 (pad 8), 64 (mod 256) bytes in fp32 (pad 4), spreads them over the banks
 template <typename T>
@@ -179,30 +173,6 @@ __global__ __launch_bounds__(256) void copy_cols_masked_kernel(double* __restric
   if (t >= rows * k) return;
   const int64_t r = t / k, j = t % k;
   if (mask[j] != 0) dst[r * ldd + j] = src[r * lds + j];
-}
-
-int g_rhs_splitk = 0;  // set_rhs_splitk
-
-struct RhsPlan {
-  int64_t tiles, rows_pad, kchunk;
-  int S;
-};
-
-RhsPlan rhs_plan(const Layout& L) {
-  RhsPlan pl;
-  pl.tiles = std::max<int64_t>((L.rows + kRhsTileM - 1) / kRhsTileM, 1);
-  pl.rows_pad = pl.tiles * kRhsTileM;
-  int64_t S = g_rhs_splitk;
-  if (S <= 0) {
-    // memory-bound: about two workgroups per CU keep HBM busy; a K-slice of at least 256 columns
-    S = (2 * (int64_t)num_cus() + pl.tiles - 1) / pl.tiles;
-    S = std::min<int64_t>(S, std::max<int64_t>(L.n / 256, 1));
-  }
-  S = std::max<int64_t>(1, std::min<int64_t>(S, kRhsMaxSplit));
-  // slices start on a multiple of 16 columns (the widest K step, and 16-byte aligned in both dtypes)
-  pl.kchunk = (((L.n + S - 1) / S + 15) / 16) * 16;
-  pl.S = (int)std::max<int64_t>((L.n + pl.kchunk - 1) / pl.kchunk, 1);  // no empty slice
-  return pl;
 }
 
 template <typename T, int NF>

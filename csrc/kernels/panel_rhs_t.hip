@@ -37,10 +37,6 @@ namespace kern {
 
 namespace {
 
-constexpr int kRtWaves = 4;       // waves per workgroup, each on its own columns of P
-constexpr int kRtKC = 32;         // local rows per LDS stage of V
-constexpr int kRtMaxSplit = 64;
-
 // LDS row padding of V (elements) at column width kw: the 4 K lanes of a B-fragment read sit on
 // consecutive rows.  fp64: pitch = 16 (mod 32) elements, 128 (mod 256) bytes apart; fp32: pitch = 16
 // (mod 64) elements, 64 (mod 256) bytes apart.
@@ -153,21 +149,6 @@ __global__ __launch_bounds__(64 * kRtWaves) void panel_rhs_t_kernel(
         out[(int64_t)(MF::row(lane, q) * W + j) * KW + nf * 16 + i] = (double)acc[j][nf][q];
 }
 
-// Pass 2: one thread per element of S (c < n, j < k).
-template <int KW>
-__global__ __launch_bounds__(256) void panel_rhs_t_reduce(const double* __restrict__ part, int S, int64_t cols_pad,
-                                                          int64_t n, int k, double* __restrict__ out, int64_t lds,
-                                                          const int32_t* __restrict__ active) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t c = t / KW;
-  const int j = (int)(t % KW);
-  if (c >= n || j >= k) return;
-  double sum = 0.0;
-  if (!active || active[j] != 0)
-    for (int s = 0; s < S; ++s) sum += part[((int64_t)s * cols_pad + c) * KW + j];
-  out[c * lds + j] = sum;
-}
-
 // colmax of the active columns starts from 0 (the integer key of +0.0)
 __global__ void axpy_cols_init_kernel(unsigned long long* colmax, int k, const int32_t* __restrict__ active) {
   const int j = threadIdx.x;
@@ -190,36 +171,6 @@ __global__ __launch_bounds__(256) void col_abs_sum_kernel(const T* __restrict__ 
   if (rs == 0 && c < n) out[c] = ((sh[0][cl] + sh[1][cl]) + sh[2][cl]) + sh[3][cl];
 }
 
-int g_rt_split = 0;  // set_rhs_t_split
-
-struct RtPlan {
-  int64_t tiles, cols_pad, rchunk, real;
-  int S, W;
-  bool vec;
-};
-
-RtPlan rt_plan(DType dt, const void* P, int64_t ldp, const Layout& L) {
-  RtPlan pl;
-  // 16-byte loads of P need 16-byte aligned rows; a lane's columns start on a multiple of W
-  pl.vec = rows_16B_aligned(P, ldp, dtype_size(dt));
-  pl.W = pl.vec ? (int)(16 / dtype_size(dt)) : 1;
-  const int64_t tw = 16 * pl.W * kRtWaves;
-  pl.tiles = std::max<int64_t>((L.n + tw - 1) / tw, 1);
-  pl.cols_pad = pl.tiles * tw;
-  pl.real = L.real_rows();
-  int64_t S = g_rt_split;
-  if (S <= 0) {
-    // memory-bound: about two workgroups per CU keep HBM busy; a slice of at least 128 rows
-    S = (2 * (int64_t)num_cus() + pl.tiles - 1) / pl.tiles;
-    S = std::min<int64_t>(S, std::max<int64_t>(pl.real / 128, 1));
-  }
-  S = std::max<int64_t>(1, std::min<int64_t>(S, kRtMaxSplit));
-  // slices are whole K steps of 4 rows
-  pl.rchunk = std::max<int64_t>((((pl.real + S - 1) / S + 3) / 4) * 4, 4);
-  pl.S = (int)std::max<int64_t>((pl.real + pl.rchunk - 1) / pl.rchunk, 1);  // no empty slice
-  return pl;
-}
-
 template <typename T, int NF>
 void launch_rt(const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int k,
                const int32_t* active, double* part, const RtPlan& pl, hipStream_t s) {
@@ -230,14 +181,6 @@ void launch_rt(const void* P, int64_t ldp, const Layout& L, const double* V, int
   else
     hipLaunchKernelGGL((panel_rhs_t_kernel<T, NF, 1>), grid, block, 0, s, static_cast<const T*>(P), ldp, pl.real,
                        L.n, (uint32_t)L.m, L.p, L.k, V, ldv, k, active, part, pl.cols_pad, pl.rchunk);
-}
-
-template <int KW>
-void launch_rt_reduce(const double* part, const RtPlan& pl, const Layout& L, int k, double* S, int64_t lds,
-                      const int32_t* active, hipStream_t s) {
-  const int64_t work = L.n * KW;
-  hipLaunchKernelGGL((panel_rhs_t_reduce<KW>), dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, part, pl.S,
-                     pl.cols_pad, L.n, k, S, lds, active);
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
-// Shared pieces of the skinny-block kernels (panel_rhs.hip, panel_rhs_t.hip, rank_update.hip): a
-// tall panel against a skinny fp64 block of at most 64 columns.  The MFMA traits, the NaN-keeping
-// magnitude key, the host-side launch helpers and the column epilogue Y = C_in + sign * term with
-// its column maxima.
+// Shared pieces of the skinny-block kernels (panel_rhs.hip, panel_rhs_t.hip, panel_abs.hip,
+// rank_update.hip): a tall panel against a skinny fp64 block of at most 64 columns.  The MFMA traits,
+// the NaN-keeping magnitude key, the host-side launch helpers, the split plans of the two streaming
+// products, the column epilogue Y = C_in + sign * term with its column maxima and the slice sum of
+// the transposed products.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,6 +14,7 @@
 #include <type_traits>
 
 #include "gj/common.hpp"
+#include "gj/layout.hpp"
 
 namespace gj {
 namespace kern {
@@ -81,6 +83,71 @@ inline int padded_kw(int64_t k) {
   return with_kw(k, [](auto KW) -> int { return KW; });
 }
 
+// The shapes and split plans of the two streaming products, shared by each product and its sibling
+// of absolute values (panel_rhs.hip / panel_rhs_t.hip / panel_abs.hip).
+constexpr int kRhsMI = 2;                             // 16-row fragments per wave
+constexpr int kRhsWaves = 4;                          // waves per workgroup
+constexpr int kRhsTileM = 16 * kRhsMI * kRhsWaves;    // 128 rows per workgroup
+constexpr int kRhsKC = 32;                            // rows of V per LDS stage
+constexpr int kRhsMaxSplit = 64;
+constexpr int kRtWaves = 4;       // waves per workgroup, each on its own columns of P
+constexpr int kRtKC = 32;         // local rows per LDS stage of V
+constexpr int kRtMaxSplit = 64;
+
+inline int g_rhs_splitk = 0;  // set_rhs_splitk
+inline int g_rt_split = 0;    // set_rhs_t_split
+
+// P (rows x n) V: row tiles of kRhsTileM and S K-slices of kchunk columns
+struct RhsPlan {
+  int64_t tiles, rows_pad, kchunk;
+  int S;
+};
+inline RhsPlan rhs_plan(const Layout& L) {
+  RhsPlan pl;
+  pl.tiles = std::max<int64_t>((L.rows + kRhsTileM - 1) / kRhsTileM, 1);
+  pl.rows_pad = pl.tiles * kRhsTileM;
+  int64_t S = g_rhs_splitk;
+  if (S <= 0) {
+    // memory-bound: about two workgroups per CU keep HBM busy; a K-slice of at least 256 columns
+    S = (2 * (int64_t)num_cus() + pl.tiles - 1) / pl.tiles;
+    S = std::min<int64_t>(S, std::max<int64_t>(L.n / 256, 1));
+  }
+  S = std::max<int64_t>(1, std::min<int64_t>(S, kRhsMaxSplit));
+  // slices start on a multiple of 16 columns (the widest K step, and 16-byte aligned in both dtypes)
+  pl.kchunk = (((L.n + S - 1) / S + 15) / 16) * 16;
+  pl.S = (int)std::max<int64_t>((L.n + pl.kchunk - 1) / pl.kchunk, 1);  // no empty slice
+  return pl;
+}
+
+// P^T V over the local rows: column tiles of 64 W (W = elements of P per load) and S row slices of
+// rchunk rows
+struct RtPlan {
+  int64_t tiles, cols_pad, rchunk, real;
+  int S, W;
+  bool vec;
+};
+inline RtPlan rt_plan(DType dt, const void* P, int64_t ldp, const Layout& L) {
+  RtPlan pl;
+  // 16-byte loads of P need 16-byte aligned rows; a lane's columns start on a multiple of W
+  pl.vec = rows_16B_aligned(P, ldp, dtype_size(dt));
+  pl.W = pl.vec ? (int)(16 / dtype_size(dt)) : 1;
+  const int64_t tw = 16 * pl.W * kRtWaves;
+  pl.tiles = std::max<int64_t>((L.n + tw - 1) / tw, 1);
+  pl.cols_pad = pl.tiles * tw;
+  pl.real = L.real_rows();
+  int64_t S = g_rt_split;
+  if (S <= 0) {
+    // memory-bound: about two workgroups per CU keep HBM busy; a slice of at least 128 rows
+    S = (2 * (int64_t)num_cus() + pl.tiles - 1) / pl.tiles;
+    S = std::min<int64_t>(S, std::max<int64_t>(pl.real / 128, 1));
+  }
+  S = std::max<int64_t>(1, std::min<int64_t>(S, kRtMaxSplit));
+  // slices are whole K steps of 4 rows
+  pl.rchunk = std::max<int64_t>((((pl.real + S - 1) / S + 3) / 4) * 4, 4);
+  pl.S = (int)std::max<int64_t>((pl.real + pl.rchunk - 1) / pl.rchunk, 1);  // no empty slice
+  return pl;
+}
+
 // Formats the probe name of op Op's launch into that op's buffer of this thread and points `last`
 // (the op's g_last_*_kernel) at it.
 template <typename Op>
@@ -120,7 +187,8 @@ struct DenseTerm {
 // Y = C_in + sign * term on the active columns c < k of the rows < rows, and the maxima of |Y| of
 // the rows that count, as keys (nonneg_key) into colmax, which the caller has set to 0 for the active
 // columns.  A workgroup covers rpb rows x KW columns (thread = column tid % KW, row group tid / KW).
-template <int KW, typename Src>
+// AbsC: |C_in| takes the place of C_in (the products of absolute values, panel_abs.hip).
+template <int KW, typename Src, bool AbsC = false>
 __global__ __launch_bounds__(256) void col_epilogue_kernel(Src src, const double* C_in, int64_t ldc, double* Y,
                                                            int64_t ldy, double sign, int64_t rows, int k,
                                                            const int32_t* __restrict__ active,
@@ -135,6 +203,7 @@ __global__ __launch_bounds__(256) void col_epilogue_kernel(Src src, const double
     for (int64_t r = base + rs; r < end; r += RG) {
       const bool counts = src.counts(r);
       double y = C_in ? C_in[r * ldc + c] : 0.0;
+      if (AbsC) y = fabs(y);
       if (counts) {
         y += sign * src.term(r, c);
         const unsigned long long kk = nonneg_key(fabs(y));
@@ -153,14 +222,38 @@ __global__ __launch_bounds__(256) void col_epilogue_kernel(Src src, const double
   }
 }
 
-template <int KW, typename Src>
+template <int KW, typename Src, bool AbsC = false>
 inline void launch_col_epilogue(const Src& src, const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign,
                                 int64_t rows, int k, const int32_t* active, unsigned long long* colmax,
                                 hipStream_t s) {
   const int rpb = 4 * (256 / KW);
   const unsigned grid = (unsigned)std::max<int64_t>((rows + rpb - 1) / rpb, 1);
-  hipLaunchKernelGGL((col_epilogue_kernel<KW, Src>), dim3(grid), dim3(256), 0, s, src, C_in, ldc, Y, ldy, sign, rows,
+  hipLaunchKernelGGL((col_epilogue_kernel<KW, Src, AbsC>), dim3(grid), dim3(256), 0, s, src, C_in, ldc, Y, ldy, sign, rows,
                      k, active, colmax, rpb);
+}
+
+// Pass 2 of the transposed products: S = sum_{slice} part in slice order (+0.0 for an inactive
+// column), one thread per element of S (c < n, j < k).
+template <int KW>
+__global__ __launch_bounds__(256) void panel_rhs_t_reduce(const double* __restrict__ part, int S, int64_t cols_pad,
+                                                          int64_t n, int k, double* __restrict__ out, int64_t lds,
+                                                          const int32_t* __restrict__ active) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t c = t / KW;
+  const int j = (int)(t % KW);
+  if (c >= n || j >= k) return;
+  double sum = 0.0;
+  if (!active || active[j] != 0)
+    for (int s = 0; s < S; ++s) sum += part[((int64_t)s * cols_pad + c) * KW + j];
+  out[c * lds + j] = sum;
+}
+
+template <int KW>
+inline void launch_rt_reduce(const double* part, const RtPlan& pl, const Layout& L, int k, double* S, int64_t lds,
+                             const int32_t* active, hipStream_t s) {
+  const int64_t work = L.n * KW;
+  hipLaunchKernelGGL((panel_rhs_t_reduce<KW>), dim3((unsigned)((work + 255) / 256)), dim3(256), 0, s, part, pl.S,
+                     pl.cols_pad, L.n, k, S, lds, active);
 }
 
 }  // namespace kern

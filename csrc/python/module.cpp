@@ -13,6 +13,7 @@
 #include <memory>
 #include <tuple>
 
+#include "gj/async_host_device.hpp"
 #include "gj/comms.hpp"
 #include "gj/engine.hpp"
 #include "gj/hip_device.hpp"
@@ -175,13 +176,18 @@ py::array_t<double> to_array(const std::vector<double>& v, int64_t r, int64_t c)
 
 }  // namespace
 
-static py::dict rhs_info(const RhsResult& rr) {
+// bounds: the solve was asked for ferr / berr (the keys are absent otherwise)
+static py::dict rhs_info(const RhsResult& rr, bool bounds = false) {
   py::dict info;
   info["residual"] = rr.residual;
   info["backward_error"] = rr.backward_error;
   info["history"] = rr.history;
   info["steps"] = rr.steps;
   info["converged"] = rr.converged;
+  if (bounds) {
+    info["ferr"] = rr.ferr;
+    info["berr"] = rr.berr;
+  }
   return info;
 }
 
@@ -261,7 +267,11 @@ PYBIND11_MODULE(_C, mod) {
   mod.def("last_rhs_t_kernel", [] { return std::string(kern::last_rhs_t_kernel()); },
           "test probe: 'rhst<16|32|64>:<f64|f32>:<vec|scalar>:s<split>' of this thread's last Device.panel_rhs_t "
           "('host' on the host executor)");
-  mod.def("last_rank_update_kernel", [] { return std::string(kern::last_rank_update_kernel()); },
+  mod.def("last_abs_kernel", [] { return std::string(kern::last_abs_kernel()); },
+          "test probe: 'abs<16|32|64>:<f64|f32>:<vec|scalar>:s<split>' of this thread's last Device.panel_abs_rhs, "
+          "'abst...' of its last panel_abs_rhs_t ('host' on the host executors); the splits are those of "
+          "set_rhs_splitk / set_rhs_t_split");
+  mod.def("last_rank_update_kernel",[] { return std::string(kern::last_rank_update_kernel()); },
           "test probe: 'rku<k padded to 4>:<f64|f32>:<vec|scalar>' of this thread's last Device.rank_update "
           "('host' on the host executor)");
   mod.def("last_slogdet_kernel", [] { return std::string(kern::last_slogdet_kernel()); },
@@ -498,6 +508,32 @@ PYBIND11_MODULE(_C, mod) {
              run(0);
              return time_launches(d, S_MAIN, reps, run);
            })
+      // The same timings of their siblings on absolute values (Y = |P| |V| with column maxima, S = |P|^T |V|)
+      .def("time_panel_abs_rhs",
+           [lay](Device& d, const std::string& dt, U P, int64_t ldp, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U V, int64_t ldv, int64_t ncols, U Y, int64_t ldy, U colmax, int reps) {
+             py::gil_scoped_release rel;
+             const Layout L = lay(n, m, p, k);
+             const DType t = parse_dtype(dt);
+             auto run = [&](int) {
+               d.panel_abs_rhs(t, (const void*)P, ldp, L, (const double*)V, ldv, ncols, nullptr, 0, (double*)Y, ldy,
+                               (double*)colmax, S_MAIN);
+             };
+             run(0);
+             return time_launches(d, S_MAIN, reps, run);
+           })
+      .def("time_panel_abs_rhs_t",
+           [lay](Device& d, const std::string& dt, U P, int64_t ldp, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U V, int64_t ldv, int64_t ncols, U S, int64_t lds, int reps) {
+             py::gil_scoped_release rel;
+             const Layout L = lay(n, m, p, k);
+             const DType t = parse_dtype(dt);
+             auto run = [&](int) {
+               d.panel_abs_rhs_t(t, (const void*)P, ldp, L, (const double*)V, ldv, ncols, (double*)S, lds, S_MAIN);
+             };
+             run(0);
+             return time_launches(d, S_MAIN, reps, run);
+           })
       // The same timing of rank_update (X -= / += W Z^T in turn, so that X stays bounded), W in local order
       .def("time_rank_update",
            [lay](Device& d, const std::string& dt, U X, int64_t ldx, int64_t n, int64_t m, int64_t p, int64_t k,
@@ -639,6 +675,40 @@ PYBIND11_MODULE(_C, mod) {
            },
            py::arg("dt"), py::arg("P"), py::arg("ldp"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"),
            py::arg("V"), py::arg("ldv"), py::arg("ncols"), py::arg("S"), py::arg("lds"), py::arg("active") = U(0))
+      // Y = |C_in| + |P| |V| in fp64 whatever dt is; 0 = a null pointer
+      .def("panel_abs_rhs",
+           [lay](Device& d, const std::string& dt, U P, int64_t ldp, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U V, int64_t ldv, int64_t ncols, U C_in, int64_t ldc, U Y, int64_t ldy, U colmax) {
+             py::gil_scoped_release rel;
+             d.panel_abs_rhs(parse_dtype(dt), (const void*)P, ldp, lay(n, m, p, k), (const double*)V, ldv, ncols,
+                             (const double*)C_in, ldc, (double*)Y, ldy, (double*)colmax, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("dt"), py::arg("P"), py::arg("ldp"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"),
+           py::arg("V"), py::arg("ldv"), py::arg("ncols"), py::arg("C_in"), py::arg("ldc"), py::arg("Y"),
+           py::arg("ldy"), py::arg("colmax") = U(0))
+      // S = |P|^T |V| over this rank's real rows, in fp64 whatever dt is
+      .def("panel_abs_rhs_t",
+           [lay](Device& d, const std::string& dt, U P, int64_t ldp, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U V, int64_t ldv, int64_t ncols, U S, int64_t lds) {
+             py::gil_scoped_release rel;
+             d.panel_abs_rhs_t(parse_dtype(dt), (const void*)P, ldp, lay(n, m, p, k), (const double*)V, ldv, ncols,
+                               (double*)S, lds, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("dt"), py::arg("P"), py::arg("ldp"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"),
+           py::arg("V"), py::arg("ldv"), py::arg("ncols"), py::arg("S"), py::arg("lds"))
+      // G = |R| + nz_eps D (+ safe1 where D <= safe2), berr[j] = max_r |R| / D (xGERFS)
+      .def("bound_terms",
+           [](Device& d, U R, int64_t ldr, U D, int64_t ldd, U G, int64_t ldg, int64_t rows, int64_t ncols,
+              double nz_eps, double safe1, double safe2, U berr) {
+             py::gil_scoped_release rel;
+             d.bound_terms((const double*)R, ldr, (const double*)D, ldd, (double*)G, ldg, rows, ncols, nz_eps, safe1,
+                           safe2, (double*)berr, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("R"), py::arg("ldr"), py::arg("D"), py::arg("ldd"), py::arg("G"), py::arg("ldg"), py::arg("rows"),
+           py::arg("ncols"), py::arg("nz_eps"), py::arg("safe1"), py::arg("safe2"), py::arg("berr"))
       // X += sign * W Z^T over this rank's real rows and the columns < n, rounded once (in place)
       .def("rank_update",
            [lay](Device& d, const std::string& dt, U X, int64_t ldx, int64_t n, int64_t m, int64_t p, int64_t k,
@@ -773,8 +843,11 @@ PYBIND11_MODULE(_C, mod) {
   mod.def("hip_device", [](int idx) { return std::shared_ptr<Device>(new HipDevice(idx)); });
   mod.def("host_device", [](int nthreads) { return std::shared_ptr<Device>(new HostDevice(nthreads)); },
           py::arg("nthreads") = 0);
+  // the asynchronous host executor (its own worker threads per stream), for per-op tests
+  mod.def("async_host_device", [](int nthreads) { return std::shared_ptr<Device>(new AsyncHostDevice(nthreads)); },
+          py::arg("nthreads") = 1);
 
-  py::class_<Comm, std::shared_ptr<Comm>>(mod, "Comm")
+  py::class_<Comm,std::shared_ptr<Comm>>(mod, "Comm")
       .def_property_readonly("size", &Comm::size)
       .def_property_readonly("rank", &Comm::rank)
       .def("describe", &Comm::describe)
@@ -1043,7 +1116,7 @@ PYBIND11_MODULE(_C, mod) {
       .def("solve_rhs_block",
            [](PyEngine& e, py::object B, py::object gen, py::object rows, uintptr_t rows_f64, int64_t ld,
               uintptr_t b_dev, int64_t ldb, uintptr_t x_dev, int64_t ldx, int64_t ncols, int max_refine,
-              double tol, bool trans) {
+              double tol, bool trans, bool bounds) {
              const int64_t n = e.eng->layout().n;
              max_refine = refine_budget(*e.eng, max_refine);
              GenSpec g;
@@ -1075,7 +1148,7 @@ PYBIND11_MODULE(_C, mod) {
                br = e.eng->solve_rhs_block_device(reinterpret_cast<const double*>(b_dev), ldb,
                                                   reinterpret_cast<double*>(x_dev), ldx, ncols, gp, hrp,
                                                   reinterpret_cast<const void*>(rows_f64), ldr, max_refine, tol,
-                                                  trans);
+                                                  trans, bounds);
              } else {
                auto b = B.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
                if (b.ndim() != 2 || b.shape(0) != n || b.shape(1) < 1)
@@ -1085,12 +1158,13 @@ PYBIND11_MODULE(_C, mod) {
                {
                  py::gil_scoped_release rel;
                  br = e.eng->solve_rhs_block(b.data(), k, x.mutable_data(), k, k, gp, hrp,
-                                             reinterpret_cast<const void*>(rows_f64), ldr, max_refine, tol, trans);
+                                             reinterpret_cast<const void*>(rows_f64), ldr, max_refine, tol, trans,
+                                             bounds);
                }
                xo = x;
              }
              py::list infos;
-             for (const RhsResult& rc : br.col) infos.append(rhs_info(rc));
+             for (const RhsResult& rc : br.col) infos.append(rhs_info(rc, bounds));
              py::dict meta;
              meta["sweeps"] = br.sweeps;
              meta["seconds"] = br.seconds;
@@ -1099,12 +1173,51 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("B") = py::none(), py::arg("gen") = py::none(), py::arg("rows") = py::none(),
            py::arg("rows_f64") = 0, py::arg("ld") = 0, py::arg("b_dev") = 0, py::arg("ldb") = 0,
            py::arg("x_dev") = 0, py::arg("ldx") = 0, py::arg("ncols") = 0, py::arg("max_refine") = -1,
-           py::arg("tol") = 1e-15, py::arg("trans") = false,
+           py::arg("tol") = 1e-15, py::arg("trans") = false, py::arg("bounds") = false,
            "A X = B (trans: A^T X = B) after solve() for a block of right-hand sides (Engine::solve_rhs_block): every "
            "column refined "
            "in fp64 against A given as gen=(kind, seed), rows (this rank's fp64 rows, host) or rows_f64 / ld (an "
            "fp64 device array).  B: an (n, k) host array -> returns (X, infos, meta); or b_dev / x_dev device "
-           "pointers (fp64, n x ncols) -> X is written in place and returned as None")
+           "pointers (fp64, n x ncols) -> X is written in place and returned as None.  bounds: every info also "
+           "carries 'ferr' and 'berr' of the returned column (RhsResult)")
+      .def("cond",
+           [](PyEngine& e, py::object gen, py::object rows, uintptr_t rows_f64, int64_t ld) {
+             const int64_t n = e.eng->layout().n;
+             GenSpec g;
+             const GenSpec* gp = nullptr;
+             if (!gen.is_none()) {
+               const py::tuple t = gen.cast<py::tuple>();
+               g.kind = parse_gen(t[0].cast<std::string>());
+               g.seed = t[1].cast<uint64_t>();
+               gp = &g;
+             }
+             py::array_t<double, py::array::c_style | py::array::forcecast> hr;
+             const double* hrp = nullptr;
+             int64_t ldr = ld;
+             if (!rows.is_none()) {
+               hr = rows.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
+               if (hr.ndim() != 2 || hr.shape(0) != e.eng->real_local_rows() || hr.shape(1) != n)
+                 throw std::invalid_argument("rows must be (real_rows, n) float64");
+               hrp = hr.data();
+               ldr = n;
+             } else if (rows_f64 && ld < n) {
+               throw std::invalid_argument("ld < n");
+             }
+             CondResult c;
+             {
+               py::gil_scoped_release rel;
+               c = e.eng->cond(gp, hrp, reinterpret_cast<const void*>(rows_f64), ldr);
+             }
+             py::dict o;
+             o["a_norm1"] = c.a_norm1;
+             o["a_norminf"] = c.a_norminf;
+             o["inv_norm1"] = c.inv_norm1;
+             o["inv_norminf"] = c.inv_norminf;
+             return o;
+           },
+           py::arg("gen") = py::none(), py::arg("rows") = py::none(), py::arg("rows_f64") = 0, py::arg("ld") = 0,
+           "the 1- and inf-norms of A (gen / rows / rows_f64 as in solve_rhs_block) and of the resident inverse "
+           "(Engine::cond; collective)")
       .def("update_inverse",
            [](PyEngine& e, py::object Uo, py::object Vo, uintptr_t u_dev, int64_t ldu, uintptr_t v_dev, int64_t ldv,
               int64_t ncols) {
@@ -1295,6 +1408,8 @@ PYBIND11_MODULE(_C, mod) {
     if (d.contains("nrhs")) c.nrhs = d["nrhs"].cast<int>();
     if (c.nrhs < 1) throw std::invalid_argument("nrhs must be >= 1");
     if (d.contains("trans")) c.trans = d["trans"].cast<bool>();
+    if (d.contains("bounds")) c.bounds = d["bounds"].cast<bool>();
+    if (d.contains("cond")) c.cond = d["cond"].cast<bool>();
     if (d.contains("keep_solution")) c.keep_solution = d["keep_solution"].cast<bool>();
     if (d.contains("comm_timeout_s")) c.solve.comm_timeout_s = d["comm_timeout_s"].cast<double>();
     if (d.contains("residual")) {
@@ -1373,6 +1488,12 @@ PYBIND11_MODULE(_C, mod) {
       o["slogdet"] = std::vector<double>{r.det.sign, r.det.logabsdet};
       o["slogdet_ranks"] = to_array(r.det_ranks, c.ranks, 2);
     }
+    if (r.cond_computed) {
+      py::dict cd;
+      cd["one"] = r.cond.a_norm1 * r.cond.inv_norm1;
+      cd["inf"] = r.cond.a_norminf * r.cond.inv_norminf;
+      o["cond"] = cd;
+    }
     if (r.rhs_solved) {
       o["axb_residual"] = r.rhs_residual;
       o["axb_seconds"] = r.rhs_seconds;
@@ -1383,9 +1504,9 @@ PYBIND11_MODULE(_C, mod) {
       o["x_head"] = r.x_head;
       if (c.keep_solution) o["x"] = to_array(r.x, c.n, r.nrhs);
       if (r.trans) o["trans"] = true;
-      if (r.nrhs > 1 || r.trans) {
+      if (r.nrhs > 1 || r.trans || r.bounds) {
         py::list cols;
-        for (const RhsResult& rc : r.rhs_cols) cols.append(rhs_info(rc));
+        for (const RhsResult& rc : r.rhs_cols) cols.append(rhs_info(rc, r.bounds));
         o["axb_columns"] = cols;
       }
     }

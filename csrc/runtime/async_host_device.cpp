@@ -367,6 +367,25 @@ void AsyncHostDevice::axpy_cols_masked(double* Y, int64_t ldy, const double* C_i
 void AsyncHostDevice::col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout& L, double* out, int s) {
   enqueue(s, [=] { inner_.col_abs_sum(dt, X, ldx, L, out, s); });
 }
+void AsyncHostDevice::panel_abs_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V,
+                                    int64_t ldv, int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy,
+                                    double* colmax, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_abs_rhs: 1 <= k <= 64 columns");
+  g_last_abs_kernel = "host";
+  enqueue(s, [=] { inner_.panel_abs_rhs(dt, P, ldp, L, V, ldv, k, C_in, ldc, Y, ldy, colmax, s); });
+}
+void AsyncHostDevice::panel_abs_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V,
+                                      int64_t ldv, int64_t k, double* S, int64_t lds, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_abs_rhs_t: 1 <= k <= 64 columns");
+  g_last_abs_kernel = "host";
+  enqueue(s, [=] { inner_.panel_abs_rhs_t(dt, P, ldp, L, V, ldv, k, S, lds, s); });
+}
+void AsyncHostDevice::bound_terms(const double* R, int64_t ldr, const double* D, int64_t ldd, double* G, int64_t ldg,
+                                  int64_t rows, int64_t k, double nz_eps, double safe1, double safe2, double* berr,
+                                  int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "bound_terms: 1 <= k <= 64 columns");
+  enqueue(s, [=] { inner_.bound_terms(R, ldr, D, ldd, G, ldg, rows, k, nz_eps, safe1, safe2, berr, s); });
+}
 void AsyncHostDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw,
                                   bool w_natural, const double* Z, int64_t ldz, int64_t k, double sign, int s) {
   GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "rank_update: 1 <= k <= 64 columns");

@@ -666,6 +666,70 @@ void HostDevice::col_abs_sum(DType dt, const void* X, int64_t ldx, const Layout&
   });
 }
 
+void HostDevice::panel_abs_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                               int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy, double* colmax,
+                               int) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_abs_rhs: 1 <= k <= 64 columns");
+  g_last_abs_kernel = "host";
+  std::vector<double> rowmax((size_t)std::max<int64_t>(L.rows, 1) * k, 0.0);
+  parallel_for(L.rows, nthreads_, [&](int64_t r) {
+    const bool real = L.global_row(r) < L.n;
+    for (int64_t j = 0; j < k; ++j) {
+      double y = C_in ? std::fabs(C_in[r * ldc + j]) : 0.0;
+      if (real) {
+        double acc = 0.0;  // fp64 for both dtypes
+        for (int64_t c = 0; c < L.n; ++c)
+          acc += std::fabs(dt == DType::F64 ? tp<double>(P)[r * ldp + c] : (double)tp<float>(P)[r * ldp + c]) *
+                 std::fabs(V[c * ldv + j]);
+        y += acc;
+        rowmax[(size_t)(r * k + j)] = y;
+      }
+      Y[r * ldy + j] = y;
+    }
+  });
+  if (!colmax) return;
+  for (int64_t j = 0; j < k; ++j) {
+    double mx = 0.0;
+    for (int64_t r = 0; r < L.rows; ++r) mx = max_keep_nan(mx, rowmax[(size_t)(r * k + j)]);
+    colmax[j] = mx;
+  }
+}
+
+void HostDevice::panel_abs_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                                 int64_t k, double* S, int64_t lds, int) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_abs_rhs_t: 1 <= k <= 64 columns");
+  g_last_abs_kernel = "host";
+  parallel_for(L.n, nthreads_, [&](int64_t c) {
+    for (int64_t j = 0; j < k; ++j) {
+      double sum = 0.0;  // fp64 for both dtypes
+      for (int64_t r = 0; r < L.rows; ++r) {
+        const int64_t g = L.global_row(r);
+        if (g >= L.n) continue;
+        sum += std::fabs(dt == DType::F64 ? tp<double>(P)[r * ldp + c] : (double)tp<float>(P)[r * ldp + c]) *
+               std::fabs(V[g * ldv + j]);
+      }
+      S[c * lds + j] = sum;
+    }
+  });
+}
+
+void HostDevice::bound_terms(const double* R, int64_t ldr, const double* D, int64_t ldd, double* G, int64_t ldg,
+                             int64_t rows, int64_t k, double nz_eps, double safe1, double safe2, double* berr, int) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "bound_terms: 1 <= k <= 64 columns");
+  for (int64_t j = 0; j < k; ++j) {
+    double mx = 0.0;
+    for (int64_t r = 0; r < rows; ++r) {
+      const double ar = std::fabs(R[r * ldr + j]), d = D[r * ldd + j];
+      const bool tiny = d <= safe2;
+      double g = std::fma(nz_eps, d, ar);  // one rounding
+      if (tiny) g += safe1;
+      G[r * ldg + j] = g;
+      mx = max_keep_nan(mx, tiny ? (ar + safe1) / (d + safe1) : ar / d);
+    }
+    berr[j] = mx;
+  }
+}
+
 void HostDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw,
                              bool w_natural, const double* Z, int64_t ldz, int64_t k, double sign, int) {
   GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "rank_update: 1 <= k <= 64 columns");

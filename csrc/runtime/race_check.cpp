@@ -806,6 +806,51 @@ void RaceCheckDevice::col_abs_sum(DType dt, const void* X, int64_t ldx, const La
   check(s, "col_abs_sum", {R(rect(X, ldx, L.n, real, (int64_t)dtype_size(dt)), "X"), W(span(out, 8 * L.n), "out")});
   inner_->col_abs_sum(dt, X, ldx, L, out, s);
 }
+void RaceCheckDevice::panel_abs_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V,
+                                    int64_t ldv, int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy,
+                                    double* colmax, int s) {
+  std::vector<Acc> a;
+  if (k >= 1 && k <= kMaxRhs) {  // (the inner device refuses any other k before it touches memory)
+    const int64_t real = L.real_rows();  // a prefix: only the last global block row is short
+    if (real > 0) a.push_back(R(rect(P, ldp, L.n, real, (int64_t)dtype_size(dt)), "P"));
+    a.push_back(R(rect(V, ldv, k, L.n, 8), "V"));
+    if (C_in && L.rows > 0) a.push_back(R(rect(C_in, ldc, k, L.rows, 8), "C_in"));
+    if (L.rows > 0) a.push_back(W(rect(Y, ldy, k, L.rows, 8), "Y"));
+    if (colmax) a.push_back(W(span(colmax, 8 * k), "colmax"));
+  }
+  check(s, "panel_abs_rhs", a);
+  inner_->panel_abs_rhs(dt, P, ldp, L, V, ldv, k, C_in, ldc, Y, ldy, colmax, s);
+}
+void RaceCheckDevice::panel_abs_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V,
+                                      int64_t ldv, int64_t k, double* S, int64_t lds, int s) {
+  std::vector<Acc> a;
+  if (k >= 1 && k <= kMaxRhs) {  // (the inner device refuses any other k before it touches memory)
+    const int64_t real = L.real_rows();  // a prefix: only the last global block row is short
+    if (real > 0) a.push_back(R(rect(P, ldp, L.n, real, (int64_t)dtype_size(dt)), "P"));
+    for (int64_t b = 0; b < L.nblk; ++b) {  // V: the row blocks this rank owns
+      const int64_t g0 = L.global_block(b) * L.m, h = std::min<int64_t>(L.m, L.n - g0);
+      if (h > 0) a.push_back(R(rect(V + g0 * ldv, ldv, k, h, 8), "V"));
+    }
+    a.push_back(W(rect(S, lds, k, L.n, 8), "S"));
+  }
+  check(s, "panel_abs_rhs_t", a);
+  inner_->panel_abs_rhs_t(dt, P, ldp, L, V, ldv, k, S, lds, s);
+}
+void RaceCheckDevice::bound_terms(const double* Rm, int64_t ldr, const double* D, int64_t ldd, double* G, int64_t ldg,
+                                  int64_t rows, int64_t k, double nz_eps, double safe1, double safe2, double* berr,
+                                  int s) {
+  std::vector<Acc> a;
+  if (k >= 1 && k <= kMaxRhs) {
+    if (rows > 0) {
+      a.push_back(R(rect(Rm, ldr, k, rows, 8), "R"));
+      a.push_back(R(rect(D, ldd, k, rows, 8), "D"));
+      a.push_back(W(rect(G, ldg, k, rows, 8), "G"));
+    }
+    a.push_back(W(span(berr, 8 * k), "berr"));
+  }
+  check(s, "bound_terms", a);
+  inner_->bound_terms(Rm, ldr, D, ldd, G, ldg, rows, k, nz_eps, safe1, safe2, berr, s);
+}
 void RaceCheckDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* Wm, int64_t ldw,
                                   bool w_natural, const double* Z, int64_t ldz, int64_t k, double sign, int s) {
   std::vector<Acc> a;

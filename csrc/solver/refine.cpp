@@ -48,12 +48,17 @@ struct ColumnRule {
   RhsResult best;  // the report of the best iterate
   double best_rn = 1e300, prev = 1e300;
   bool active = true;  // false: the column has stopped, r is its final report
+  // for the error bounds of the returned iterate: its ||x||, and whether the residual last computed
+  // (the current iterate's) is the returned iterate's own
+  double ret_xn = 0, best_xn = 0;
+  bool stale_r = false;
   // Iterate `it` has ||b - A x|| = rn and ||x|| = xn: updates the report r.  True: this iterate is
   // the one to return unless a later step says so again, the caller keeps a copy of it.
   bool step(RhsResult& r, int it, double rn, double xn, double an, double bn, int max_refine, double tol) {
     r.history.push_back(rn / bn);
     r.residual = rn;
     r.backward_error = rn / (an * xn + bn);
+    ret_xn = xn;
     if (r.backward_error <= tol) {
       r.converged = true;
       active = false;
@@ -63,12 +68,15 @@ struct ColumnRule {
     if (rn < best_rn) {
       best_rn = rn;
       best = r;
+      best_xn = xn;
       save = true;
     }
     if (it >= max_refine || (it > 0 && rn > 0.5 * prev)) {  // budget spent / not contracting
       if (rn > best_rn) {  // the best iterate (already saved), with its own residual (history kept)
         best.history = r.history;
         r = best;
+        ret_xn = best_xn;
+        stale_r = true;
       } else {  // (also a NaN residual: neither better nor worse, the current iterate stands)
         save = true;
       }
@@ -222,16 +230,17 @@ RhsResult Engine::solve_rhs_impl(const double* b, double* x, const GenSpec* gen,
 // ---------------------------------------------------------------- A X = B, a block of columns
 RhsBlockResult Engine::solve_rhs_block(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                        const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
-                                       int64_t ld, int max_refine, double tol, bool trans) {
-  return solve_rhs_block_impl(B, ldb, X, ldx, k, false, gen, host_rows, dev_rows_f64, ld, max_refine, tol, trans);
+                                       int64_t ld, int max_refine, double tol, bool trans, bool bounds) {
+  return solve_rhs_block_impl(B, ldb, X, ldx, k, false, gen, host_rows, dev_rows_f64, ld, max_refine, tol, trans,
+                              bounds);
 }
 
 RhsBlockResult Engine::solve_rhs_block_device(const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx,
                                               int64_t k, const GenSpec* gen, const double* host_rows,
                                               const void* dev_rows_f64, int64_t ld, int max_refine, double tol,
-                                              bool trans) {
+                                              bool trans, bool bounds) {
   return solve_rhs_block_impl(B_dev, ldb, X_dev, ldx, k, true, gen, host_rows, dev_rows_f64, ld, max_refine, tol,
-                             trans);
+                              trans, bounds);
 }
 
 // What A X = B and A^T X = B differ in, for the block driver.  Vb / Vx / Vr hold B, the iterate and
@@ -253,7 +262,23 @@ struct Engine::BlockPath {
       product;
   std::function<const double*(const double* norms)> all_ranks;  // the column norms over all ranks
   std::function<const double*()> result;          // `best` in natural row order
+  // The error bounds of a group whose columns have all stopped: xhat = result() (natural order), r
+  // holds b - A xhat unless redo_r says to compute it again; colmax[j] = this rank's max_i F_ij with
+  // F = |inv(A)| (|r| + nz_eps D), D = |A| |xhat| + |b|, and berr[j] = its max_i |r_i| / D_i (device,
+  // Device::kMaxRhs doubles each).  Uses x, r and Vr, which the loop has left.
+  std::function<void(int64_t kg, const double* xhat, bool redo_r, double* colmax, double* berr)> bounds;
 };
+
+namespace {
+// xGERFS's constants at order n
+struct BoundConst {
+  double nz_eps, safe1, safe2;
+  explicit BoundConst(int64_t n)
+      : nz_eps((double)(n + 1) * 0x1p-53),
+        safe1((double)(n + 1) * std::numeric_limits<double>::min()),
+        safe2(safe1 / 0x1p-53) {}
+};
+}  // namespace
 
 // A X = B: a product is this rank's rows of it (Device::panel_rhs), all-gathered into natural order.
 void Engine::block_path_plain(BlockPath& f, const double* Aw, int64_t kw) {
@@ -308,6 +333,16 @@ void Engine::block_path_plain(BlockPath& f, const double* Aw, int64_t kw) {
     gather_natural(Vx, best);
     return (const double*)Vx;
   };
+  f.bounds = [this, gather_natural, Aw, kw, n, b = f.b, D = f.x, r = f.r, Vr = f.Vr](
+                 int64_t kg, const double* xhat, bool redo_r, double* colmax, double* berr) {
+    const BoundConst c(n);
+    dev_.panel_abs_rhs(DType::F64, Aw, L_.npad, L_, xhat, kw, kg, b, kw, D, kw, nullptr, S_MAIN);
+    if (redo_r) dev_.panel_rhs(DType::F64, Aw, L_.npad, L_, xhat, kw, kg, b, kw, r, kw, -1.0, nullptr, nullptr, S_MAIN);
+    // G over r, on the real rows (a prefix of the local rows)
+    dev_.bound_terms(r, kw, D, kw, r, kw, real_local_rows(), kg, c.nz_eps, c.safe1, c.safe2, berr, S_MAIN);
+    gather_natural(Vr, r);
+    dev_.panel_abs_rhs(opt_.dtype, out_, L_.npad, L_, Vr, kw, kg, nullptr, 0, D, kw, colmax, S_MAIN);
+  };
 }
 
 // A^T X = B: every product is P_loc^T V_loc summed over the ranks, so B, X and R live in natural row
@@ -342,12 +377,31 @@ void Engine::block_path_trans(BlockPath& f, const double* Aw, int64_t kw) {
     dev_.axpy_cols_masked(dst, kw, C, kw, Sp, kw, sign, n, kg, act, colmax, S_MAIN);
   };
   f.result = [best] { return (const double*)best; };
+  // every step gives the same bits on every rank: B, xhat and r are whole and identical, the products
+  // are sums over the ranks
+  f.bounds = [this, Aw, Sp, nat, kw, n, b = f.b, D = f.x, r = f.r](int64_t kg, const double* xhat, bool redo_r,
+                                                                    double* colmax, double* berr) {
+    const BoundConst c(n);
+    dev_.panel_abs_rhs_t(DType::F64, Aw, L_.npad, L_, xhat, kw, kg, Sp, kw, S_MAIN);
+    comm_.allreduce_sum(dev_, Sp, nat, DType::F64, S_MAIN);
+    // D = |b| + |A^T| |xhat|: bound_terms' G with nz_eps = 1 and no safe2 row (berr is overwritten below)
+    dev_.bound_terms(b, kw, Sp, kw, D, kw, n, kg, 1.0, 0.0, -1.0, berr, S_MAIN);
+    if (redo_r) {
+      dev_.panel_rhs_t(DType::F64, Aw, L_.npad, L_, xhat, kw, kg, Sp, kw, nullptr, S_MAIN);
+      comm_.allreduce_sum(dev_, Sp, nat, DType::F64, S_MAIN);
+      dev_.axpy_cols_masked(r, kw, b, kw, Sp, kw, -1.0, n, kg, nullptr, nullptr, S_MAIN);
+    }
+    dev_.bound_terms(r, kw, D, kw, r, kw, n, kg, c.nz_eps, c.safe1, c.safe2, berr, S_MAIN);
+    dev_.panel_abs_rhs_t(opt_.dtype, out_, L_.npad, L_, r, kw, kg, Sp, kw, S_MAIN);
+    comm_.allreduce_sum(dev_, Sp, nat, DType::F64, S_MAIN);
+    dev_.axpy_cols_masked(D, kw, nullptr, kw, Sp, kw, 1.0, n, kg, nullptr, colmax, S_MAIN);
+  };
 }
 
 RhsBlockResult Engine::solve_rhs_block_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                            bool on_device, const GenSpec* gen, const double* host_rows,
                                            const void* dev_rows, int64_t ld, int max_refine, double tol,
-                                           bool trans) {
+                                           bool trans, bool bounds) {
   GJ_REQUIRE(solved_, "solve_rhs_block: solve() first");
   GJ_REQUIRE(k >= 1 && ldb >= k && ldx >= k, "solve_rhs_block: k >= 1 columns, ldb >= k and ldx >= k");
   GJ_REQUIRE(gen || host_rows || dev_rows || real_local_rows() == 0,
@@ -426,11 +480,56 @@ RhsBlockResult Engine::solve_rhs_block_impl(const double* B, int64_t ldb, double
       f.product(opt_.dtype, out_, f.Vr, kg, f.x, f.x, f.Vx, 1.0, dflag, dnorm + K);
     }
     // every column's returned iterate is in `best`
-    dev_.copy2d(X + c0, ldx * 8, f.result(), kw * 8, kg * 8, n, S_MAIN);
+    const double* xhat = f.result();
+    dev_.copy2d(X + c0, ldx * 8, xhat, kw * 8, kg * 8, n, S_MAIN);
+    if (bounds) {
+      bool redo_r = false;
+      for (const ColumnRule& c : rule) redo_r = redo_r || c.stale_r;
+      f.bounds(kg, xhat, redo_r, dnorm, dnorm + K);
+      dev_.copy(hnorm, dnorm, sizeof(double) * 2 * K, S_MAIN);
+      comm_.drain(dev_, S_MAIN);
+      dev_.host_access(hnorm, sizeof(double) * 2 * K, false);
+      const double* norms = f.all_ranks ? f.all_ranks(hnorm) : hnorm;
+      for (int64_t j = 0; j < kg; ++j) {
+        const double xn = rule[(size_t)j].ret_xn;
+        rr[j].ferr = xn == 0 ? norms[j] : norms[j] / xn;  // (LAPACK's rule for x = 0)
+        rr[j].berr = norms[K + j];
+      }
+    }
     comm_.drain(dev_, S_MAIN);
   }
   out.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return out;
+}
+
+// ---------------------------------------------------------------- ||A|| and ||inv(A)||, 1 and inf
+CondResult Engine::cond(const GenSpec* gen, const double* host_rows, const void* dev_rows, int64_t ld) {
+  GJ_REQUIRE(solved_, "cond: solve() first");
+  GJ_REQUIRE(gen || host_rows || dev_rows || real_local_rows() == 0,
+             "cond: the matrix (generator or rows) is needed for its norms");
+  const int64_t n = L_.n;
+  BufSet bufs(dev_);
+  double* Aw = bufs.get<double>((size_t)std::max<int64_t>(L_.rows, 1) * L_.npad, false);
+  stage_rows_f64(Aw, gen, host_rows, dev_rows, ld);
+  double* csum = bufs.get<double>(2 * (size_t)std::max<int64_t>(n, 1));  // column sums of A | of inv(A)
+  double* rmax = bufs.get<double>(2);                                    // row-sum maxima of A, of inv(A)
+  dev_.col_abs_sum(DType::F64, Aw, L_.npad, L_, csum, S_MAIN);
+  dev_.col_abs_sum(opt_.dtype, out_, L_.npad, L_, csum + n, S_MAIN);
+  comm_.allreduce_sum(dev_, csum, 2 * (size_t)n, DType::F64, S_MAIN);
+  dev_.row_abs_max(DType::F64, Aw, L_.npad, L_, rmax, S_MAIN);
+  dev_.row_abs_max(opt_.dtype, out_, L_.npad, L_, rmax + 1, S_MAIN);
+  std::vector<double> h(2 * (size_t)n + 2);
+  dev_.copy(h.data(), csum, sizeof(double) * 2 * (size_t)n, S_MAIN);
+  dev_.copy(h.data() + 2 * n, rmax, sizeof(double) * 2, S_MAIN);
+  comm_.drain(dev_, S_MAIN);
+  CondResult c;
+  for (int64_t j = 0; j < n; ++j) {
+    c.a_norm1 = max_keep_nan(c.a_norm1, h[(size_t)j]);
+    c.inv_norm1 = max_keep_nan(c.inv_norm1, h[(size_t)(n + j)]);
+  }
+  c.a_norminf = comm_.host_max(dev_, L_.nblk > 0 ? h[(size_t)(2 * n)] : 0.0);
+  c.inv_norminf = comm_.host_max(dev_, L_.nblk > 0 ? h[(size_t)(2 * n + 1)] : 0.0);
+  return c;
 }
 
 // ---------------------------------------------------------------- inv(A + U V^T) from inv(A)

@@ -186,6 +186,14 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
     sh.rep.det_ranks[(size_t)(2 * rank + 1)] = dr.logabsdet;
     if (rank == 0) sh.rep.det = dr;
   }
+  if (cfg.cond) {
+    const CondResult cr = eng->cond(have_rows ? nullptr : &cfg.gen, have_rows ? local.data() : nullptr, nullptr, cfg.n);
+    if (rank == 0) {
+      std::lock_guard<std::mutex> lk(sh.mu);
+      sh.rep.cond_computed = true;
+      sh.rep.cond = cr;
+    }
+  }
   if (cfg.want_corners) {
     auto c = eng->corner(nm, 1);
     if (rank == 0) {
@@ -213,7 +221,7 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
       res = eng->residual_generated(cfg.gen);
     }
   }
-  if (!sh.b.empty() && (cfg.nrhs > 1 || cfg.trans)) {  // trans: the block path at any width
+  if (!sh.b.empty() && (cfg.nrhs > 1 || cfg.trans || cfg.bounds)) {  // trans, bounds: the block path at any width
     const int64_t k = cfg.nrhs;
     std::vector<double> x((size_t)cfg.n * k);
     comm->barrier(*dev);
@@ -222,7 +230,7 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
     if (src && local.empty()) load();  // the fp64 rows of A (residual_rows keeps them in `local`)
     const RhsBlockResult br = eng->solve_rhs_block(sh.b.data(), k, x.data(), k, k, have_rows ? nullptr : &cfg.gen,
                                                    have_rows ? local.data() : nullptr, nullptr, cfg.n, refine,
-                                                   cfg.refine_tol, cfg.trans);
+                                                   cfg.refine_tol, cfg.trans, cfg.bounds);
     const double tx = comm->host_max(
         *dev, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     if (rank == 0) {
@@ -231,6 +239,7 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
       r.rhs_solved = true;
       r.nrhs = (int)k;
       r.trans = cfg.trans;
+      r.bounds = cfg.bounds;
       r.rhs_cols = br.col;
       r.rhs_converged = true;
       size_t worst = 0;

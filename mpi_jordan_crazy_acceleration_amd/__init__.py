@@ -16,13 +16,14 @@ Python entry points:
 ``solve(A, b, block_size)``            solve A x = b via the inverse             -> models.gauss_jordan
 ``factor(A, block_size)``              invert once, then .solve(b, trans=) many  -> models.gauss_jordan
 ``slogdet(A)`` / ``det(A)``            determinant from the same inversion       -> models.gauss_jordan
+``cond(A, p)``                         ||A||_p ||inv(A)||_p, p = 1 or inf        -> models.gauss_jordan
 ``run(n, m, ...)``                     the CLI flow in-process (report dict)     -> models.gauss_jordan
 ``DistributedGaussJordan``             one rank per process over torch.distributed -> parallel.dist
 ``ops``                                kernel-level wrappers (tests, profiling)
 """
 from ._native import load_native, native_available, native_path  # noqa: F401
-from .models.gauss_jordan import (Factored, GaussJordan, SingularMatrixError, det, factor, inverse,  # noqa: F401
-                                 run, slogdet, solve)
+from .models.gauss_jordan import (Factored, GaussJordan, SingularMatrixError, cond, det, factor,  # noqa: F401
+                                 inverse, run, slogdet, solve)
 from .parallel.dist import DistributedGaussJordan  # noqa: F401
 
 __version__ = "0.1.0"

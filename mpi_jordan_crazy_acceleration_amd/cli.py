@@ -16,6 +16,16 @@ from the pivot blocks, ``DistributedGaussJordan.slogdet``), and ``"slogdet"`` in
 ``--equilibrate``: power-of-two row and column scaling ahead of the sweep, undone on the inverse
 (``DistributedGaussJordan(equilibrate=True)``); stdout keeps its form (the A corner is the matrix as
 given, the residual is against it) and ``--json`` gains ``"equilibrate"``.
+``--rhs ones|random`` with ``--nrhs K``, ``--trans``, ``--bounds``: the right-hand sides of ``build/gj``
+(column j is (j+1) * ones, or seeded by seed + j), solved as a block by
+``DistributedGaussJordan.solve_rhs`` -- ``solution x:``, the head of column 0 and ``Ax-b residual: %e``
+(``ATx-b`` with ``--trans``; the maximum over the columns) as there; ``--bounds`` leaves stdout alone and
+adds ``"axb_ferr_cols"`` / ``"axb_berr_cols"`` to ``--json``.  (One right-hand side without ``--trans``
+or ``--bounds`` runs the one-vector path in ``build/gj`` and the block path here.)  With a file the
+fp64 residual re-reads the rank's rows from it.
+``--cond``: one more line ``cond: %e %e`` (kappa_1 and kappa_inf, ``DistributedGaussJordan.cond``) after
+the residual line, and after the slogdet line when both are given; ``"cond": {"one", "inf"}`` in
+``--json``.
 ``--comm-timeout S``: a rank waiting longer than S seconds on a peer fails (every rank, naming the
 step, phase and collective).  ``--same-gpu``: rehearse the p-rank RCCL path with every rank on
 GPU 0 (each rank its own RCCL host over loopback sockets; functional check, not a timing).
@@ -49,6 +59,26 @@ def _corner(c) -> str:
     return "".join("".join(f"{v:.2f}\t" for v in row) + "\n" for row in c)
 
 
+def _rhs_block(kind: str, n: int, nrhs: int, seed: int):
+    """The right-hand sides of build/gj --rhs ones|random --nrhs K (csrc/solver/runner.cpp): column j is
+    (j + 1) * ones, or column 0 of the "random" generator seeded by (seed + j) ^ 0x9E3779B97F4A7C15."""
+    import numpy as np
+
+    from .utils.reference import _MASK, _splitmix64
+
+    if kind == "ones":
+        return np.tile(np.arange(1, nrhs + 1, dtype=np.float64), (n, 1))
+    B = np.empty((n, nrhs))
+    i = np.arange(n, dtype=np.uint64)
+    for j in range(nrhs):
+        sj = ((seed + j) & _MASK) ^ 0x9E3779B97F4A7C15
+        with np.errstate(over="ignore"):
+            s = (np.uint64(sj) * np.uint64(0x2545F4914F6CDD1D)) & np.uint64(_MASK)
+            h = _splitmix64(s ^ (i << np.uint64(32)))
+        B[:, j] = (h >> np.uint64(11)).astype(np.float64) * (2.0 / 9007199254740992.0) - 1.0
+    return B
+
+
 def main(argv=None) -> int:
     import argparse
 
@@ -73,6 +103,11 @@ def main(argv=None) -> int:
     ap.add_argument("--det", action="store_true")
     ap.add_argument("--equilibrate", action="store_true")
     ap.add_argument("--same-gpu", action="store_true")
+    ap.add_argument("--rhs", choices=["ones", "random"], default=None)
+    ap.add_argument("--nrhs", type=int, default=1)
+    ap.add_argument("--trans", action="store_true")
+    ap.add_argument("--bounds", action="store_true")
+    ap.add_argument("--cond", action="store_true")
     try:
         args, unknown = ap.parse_known_args(argv)
     except SystemExit:
@@ -80,7 +115,7 @@ def main(argv=None) -> int:
     if unknown or not (2 <= len(args.pos) <= 3):
         return _usage(prog)
     n, m = _atoi(args.pos[0]), _atoi(args.pos[1])
-    if n <= 0 or m <= 0 or args.print_max < 0:
+    if n <= 0 or m <= 0 or args.print_max < 0 or args.nrhs < 1:
         return _usage(prog)
     path = args.pos[2] if len(args.pos) == 3 else None
     if args.bcast:
@@ -180,6 +215,23 @@ def main(argv=None) -> int:
             sld = solver.slogdet()
             sign = "nan" if sld[0] != sld[0] else f"{int(sld[0]):d}"
             out(f"slogdet: {sign} {sld[1]:.15e}\n")
+        a_rows, a_gen = None, (args.gen, args.seed)
+        if path is not None and (args.cond or args.rhs):  # this rank's fp64 rows, from the file again
+            ids = [int(r) for r in solver.global_row_ids()]
+            a_rows, a_gen = C.read_matrix_rows(path, n, ids, args.host_threads), None
+        kappa = None
+        if args.cond:  # as build/gj --cond: after the residual line and the slogdet line
+            kappa = [solver.cond(p, A_rows=a_rows, gen=a_gen) for p in (1, float("inf"))]
+            out(f"cond: {kappa[0]:e} {kappa[1]:e}\n")
+        infos = None
+        if args.rhs:
+            x, infos = solver.solve_rhs(_rhs_block(args.rhs, n, args.nrhs, args.seed), A_rows=a_rows, gen=a_gen,
+                                        trans=args.trans, bounds=args.bounds)
+            worst = 0.0
+            for c in infos:  # the maximum over the columns, NaN kept
+                worst = c["residual"] if c["residual"] != c["residual"] or c["residual"] > worst else worst
+            out("solution x:\n" + "".join(f"{v:.2f}\t" for v in x.reshape(n, -1)[:nm, 0]) +
+                f"\n{'ATx-b' if args.trans else 'Ax-b'} residual: {worst:e}\n")
         if args.json and rank == 0:
             rec = {"n": n, "m": m, "ranks": world, "device": "gpu" if gpu else "cpu",
                    "dtype": args.dtype, "status": st["status"], "glob_time": glob,
@@ -189,6 +241,15 @@ def main(argv=None) -> int:
                 rec["equilibrate"] = {k: (list(v) if isinstance(v, tuple) else v) for k, v in st["equilibrate"].items()}
             if sld is not None:
                 rec["slogdet"] = [v if v - v == 0 else None for v in sld]  # JSON has no NaN or Infinity
+            if kappa is not None:
+                rec["cond"] = {"one": kappa[0] if kappa[0] - kappa[0] == 0 else None,
+                               "inf": kappa[1] if kappa[1] - kappa[1] == 0 else None}
+            if infos is not None:
+                rec["axb_residual"] = worst if worst - worst == 0 else None
+                rec["nrhs"] = args.nrhs
+                if args.bounds:
+                    for key in ("ferr", "berr"):
+                        rec[f"axb_{key}_cols"] = [c[key] if c[key] - c[key] == 0 else None for c in infos]
             print(json.dumps(rec), file=sys.stderr, flush=True)
         return 0
     finally:

@@ -78,7 +78,8 @@ class GaussJordan:
     def run(self, n: int, gen: str = "absdiff", seed: int = 0, file: Optional[str] = None,
             input: Optional[np.ndarray] = None, keep_inverse: bool = False, repeats: int = 1,
             rhs=None, keep_solution: bool = False, profile: bool = False, nrhs: int = 1,
-            trans: bool = False, update=None, det: bool = False) -> dict:
+            trans: bool = False, update=None, det: bool = False, bounds: bool = False,
+            cond: bool = False) -> dict:
         """One CLI-equivalent run.  ``rhs``: None, "ones", "random", a file path, an n-vector or an
         n x k matrix — then x = inv(A) b is computed on the devices, refined in fp64, and
         ``axb_residual`` = ||A x - b||_inf reported.  ``nrhs`` > 1 (implied by a matrix): the block
@@ -92,6 +93,11 @@ class GaussJordan:
         ``det``: the report gains ``slogdet`` = [sign, logabsdet] of the matrix the inverse belongs to
         (Engine::slogdet; after the update, if one is given) and ``slogdet_ranks``, every rank's pair
         (ranks x 2: the same bits in every row).
+        ``bounds`` (with ``rhs``): every entry of ``axb_columns`` gains ``ferr`` and ``berr`` of its
+        column (the forward error bound and the componentwise backward error of LAPACK's xGERFS); one
+        right-hand side then takes the block path as one column.
+        ``cond``: the report gains ``cond`` = {"one", "inf"}, the condition numbers
+        ||A||_p ||inv(A)||_p of the matrix the inverse belongs to (after the update, if one is given).
         With ``equilibrate`` the report gains ``equilibrate`` = {applied, row_exp_range, col_exp_range}."""
         cfg = self._cfg(n)
         if det:
@@ -112,6 +118,10 @@ class GaussJordan:
         cfg["nrhs"] = int(nrhs)
         if trans:
             cfg["trans"] = True
+        if bounds:
+            cfg["bounds"] = True
+        if cond:
+            cfg["cond"] = True
         if update is not None:
             u, v = (np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t, dtype=np.float64)
                     for t in update)
@@ -176,27 +186,30 @@ class GaussJordan:
         """Invert A once and keep the engine: see :func:`factor`."""
         return Factored(self, A)
 
-    def solve_resident(self, A: torch.Tensor, b, max_refine: int = -1, tol: float = 1e-15, trans: bool = False):
+    def solve_resident(self, A: torch.Tensor, b, max_refine: int = -1, tol: float = 1e-15, trans: bool = False,
+                       bounds: bool = False):
         """A x = b for a CUDA tensor A through the engine (Engine::solve_rhs_device): x = inv(A) b by
         the native GEMV, then iterative refinement with the residual b - A x in fp64 against A's
         rows (an fp32 inverse refines to fp64 accuracy on a well-conditioned system, as the CLI's
         --rhs path).  b: an n-vector, or an n x k matrix: then Engine::solve_rhs_block refines all
         columns together on the device (one pass over each matrix per sweep, B and X never leave the
         GPU).  ``trans``: A^T x = b from the same inverse, always by the block path (a vector is one
-        column).  Returns (x on A's device in A's dtype with b's shape, info per column)."""
+        column).  ``bounds``: every info gains ``ferr`` / ``berr`` (see :class:`Factored`), also by the
+        block path.  Returns (x on A's device in A's dtype with b's shape, info per column)."""
         eng, _ = self._engine_resident(A)
         a64 = A.detach().to(torch.float64).contiguous()
-        return _solve_on_device(eng, a64, A.dtype, b, max_refine, tol, trans)
+        return _solve_on_device(eng, a64, A.dtype, b, max_refine, tol, trans, bounds)
 
 
-def _solve_on_device(eng, a64: torch.Tensor, out_dtype, b, max_refine: int, tol: float, trans: bool):
+def _solve_on_device(eng, a64: torch.Tensor, out_dtype, b, max_refine: int, tol: float, trans: bool,
+                     bounds: bool = False):
     """solve_resident's solve against an engine that holds inv(A); a64 = A's rows in fp64 on the GPU,
     x is returned there in out_dtype"""
-    if trans and np.ndim(b) == 1:
+    if (trans or bounds) and np.ndim(b) == 1:
         bt = b.detach() if isinstance(b, torch.Tensor) else torch.as_tensor(np.asarray(b, dtype=np.float64))
-        x, infos = _solve_on_device(eng, a64, out_dtype, bt.reshape(-1, 1), max_refine, tol, True)
+        x, infos = _solve_on_device(eng, a64, out_dtype, bt.reshape(-1, 1), max_refine, tol, trans, bounds)
         return x.reshape(-1), infos
-    if not trans and (np.ndim(b) != 2 or np.shape(b)[1] == 1):  # one right-hand side: the one-vector path
+    if not (trans or bounds) and (np.ndim(b) != 2 or np.shape(b)[1] == 1):  # one right-hand side: the one-vector path
         torch.cuda.synchronize(a64.device)
         bt = b.detach().to("cpu", torch.float64) if isinstance(b, torch.Tensor) else \
             torch.as_tensor(np.asarray(b, dtype=np.float64))
@@ -212,7 +225,7 @@ def _solve_on_device(eng, a64: torch.Tensor, out_dtype, b, max_refine: int, tol:
     _, infos, _ = eng.solve_rhs_block(rows_f64=a64.data_ptr(), ld=a64.stride(0), b_dev=b64.data_ptr(),
                                       ldb=b64.stride(0), x_dev=x64.data_ptr(), ldx=x64.stride(0),
                                       ncols=b64.shape[1], max_refine=int(max_refine), tol=float(tol),
-                                      trans=bool(trans))
+                                      trans=bool(trans), bounds=bool(bounds))
     return x64.to(out_dtype), list(infos)
 
 
@@ -223,7 +236,15 @@ class Factored:
     second inversion -- for an n-vector or an n x k matrix b, refined in fp64 against A's rows (which
     the object keeps in fp64); returns b's shape and type.  ``inverse()``: the inverse in A's type.
     ``n``, ``dtype`` ("fp64" | "fp32": the engine's arithmetic); ``infos``: the per-column refinement
-    results of the last solve.  A CUDA tensor A stays on its GPU (the resident engine); a numpy
+    results of the last solve.  ``solve(b, bounds=True)``: every info also holds ``ferr``, a bound of
+    ||x_true - x||_inf / ||x||_inf, and ``berr``, the componentwise backward error max_i |b - A x|_i /
+    (|A| |x| + |b|)_i -- LAPACK's xGERFS pair, with the resident |inv(A)| in place of a norm estimate
+    and fp64 arithmetic whatever the engine dtype; as there, ``ferr`` holds to first order in
+    ||I - inv(A) A|| and is to be trusted when the column's ``converged`` is true.  x is the same with
+    and without the option (a vector then takes the block path as one column).
+    ``cond(p)`` / ``rcond(p)``, p in {1, inf}: ||A||_p ||inv(A)||_p of the handle's matrix from the
+    resident inverse, and its reciprocal; cached until the next ``update``.
+    A CUDA tensor A stays on its GPU (the resident engine); a numpy
     array or a CPU tensor runs one host rank.
     ``update(U, V)``: the handle becomes that of A + U V^T (rank k <= 64) by the matrix inversion
     lemma, one pass over the inverse instead of another inversion; ``updates`` counts the updates
@@ -240,6 +261,7 @@ class Factored:
         self.infos: list = []
         self.updates = 0
         self.last_update: Optional[dict] = None
+        self._cond: Optional[dict] = None
         self._m = int(gj.block_size)
         self._a64_owned = False
         if self._is_torch and A.is_cuda:
@@ -272,22 +294,23 @@ class Factored:
         + col_exp[j]) the matrix the sweep inverted.  None when the option is off."""
         return self._eng.equil_exponents()
 
-    def solve(self, b, trans: bool = False, max_refine: int = -1, tol: float = 1e-15):
+    def solve(self, b, trans: bool = False, max_refine: int = -1, tol: float = 1e-15, bounds: bool = False):
         if self._cuda:
             out_dtype = b.dtype if isinstance(b, torch.Tensor) else self._like.dtype
-            x, self.infos = _solve_on_device(self._eng, self._a64, out_dtype, b, max_refine, tol, trans)
+            x, self.infos = _solve_on_device(self._eng, self._a64, out_dtype, b, max_refine, tol, trans, bounds)
             return x
         b_torch = isinstance(b, torch.Tensor)
         bn = b.detach().to("cpu", torch.float64).numpy() if b_torch else np.asarray(b, dtype=np.float64)
         if bn.ndim not in (1, 2) or bn.shape[0] != self.n:
             raise ValueError("b must be an n-vector or an n x k matrix")
-        if not trans and (bn.ndim == 1 or bn.shape[1] == 1):  # the one-vector path, as gj.solve
+        if not (trans or bounds) and (bn.ndim == 1 or bn.shape[1] == 1):  # the one-vector path, as gj.solve
             x, info = self._eng.solve_rhs_rows(np.ascontiguousarray(bn.reshape(-1)), self._a64, int(max_refine),
                                                float(tol))
             self.infos = [info]
         else:
             x, infos, _ = self._eng.solve_rhs_block(np.ascontiguousarray(bn.reshape(self.n, -1)), rows=self._a64,
-                                                    max_refine=int(max_refine), tol=float(tol), trans=bool(trans))
+                                                    max_refine=int(max_refine), tol=float(tol), trans=bool(trans),
+                                                    bounds=bool(bounds))
             self.infos = list(infos)
         x = x.reshape(bn.shape)
         return torch.from_numpy(x).to(device=b.device, dtype=b.dtype) if b_torch else x
@@ -341,6 +364,7 @@ class Factored:
         else:
             self._a64 = self._a64 + un @ vn.T
         self._a64_owned = True
+        self._cond = None
         res = {key: info[key] for key in ("k", "min_pivot", "cond1", "seconds")}
         self.updates += 1
         self.last_update = res
@@ -362,6 +386,25 @@ class Factored:
         sign, logabs = self.slogdet()
         with np.errstate(over="ignore"):
             return float(sign * np.exp(logabs))
+
+    def cond(self, p=np.inf) -> float:
+        """||A||_p ||inv(A)||_p for p = 1 or inf (else ValueError): the condition number of the handle's
+        matrix, with ||A|| from the kept fp64 rows and ||inv(A)|| from the resident inverse
+        (Engine::cond: exact column sums and row sums, no estimate)."""
+        if p not in (1, np.inf):
+            raise ValueError("cond: p must be 1 or inf")
+        if self._cond is None:
+            if self._cuda:
+                torch.cuda.synchronize(self._a64.device)
+                self._cond = self._eng.cond(rows_f64=self._a64.data_ptr(), ld=self._a64.stride(0))
+            else:
+                self._cond = self._eng.cond(rows=self._a64)
+        c = self._cond
+        return float(c["a_norm1"] * c["inv_norm1"] if p == 1 else c["a_norminf"] * c["inv_norminf"])
+
+    def rcond(self, p=np.inf) -> float:
+        """1 / cond(p)"""
+        return 1.0 / self.cond(p)
 
     def inverse(self):
         if self._cuda:
@@ -403,6 +446,18 @@ def slogdet(A, block_size: int = 128, **kw):
         return 0.0, float("-inf")
 
 
+def cond(A, p=np.inf, block_size: int = 128, **kw) -> float:
+    """||A||_p ||inv(A)||_p for p = 1 or inf (else ValueError) by one block Gauss-Jordan inversion
+    (:func:`factor`, then ``Factored.cond``).  A singular matrix gives inf, numpy.linalg.cond's answer,
+    instead of SingularMatrixError."""
+    if p not in (1, np.inf):
+        raise ValueError("cond: p must be 1 or inf")
+    try:
+        return factor(A, block_size=block_size, **kw).cond(p)
+    except SingularMatrixError:
+        return float("inf")
+
+
 def det(A, block_size: int = 128, **kw) -> float:
     """det A = sign * exp(logabsdet) of :func:`slogdet`; +-inf on overflow, as numpy.linalg.det."""
     sign, logabs = slogdet(A, block_size=block_size, **kw)
@@ -410,7 +465,7 @@ def det(A, block_size: int = 128, **kw) -> float:
         return float(sign * np.exp(logabs))
 
 
-def solve(A, b, block_size: int = 128, trans: bool = False, **kw):
+def solve(A, b, block_size: int = 128, trans: bool = False, bounds: bool = False, **kw):
     """Solve ``A x = b`` (``trans``: ``A^T x = b``, from the inverse of A itself) via the block
     Gauss-Jordan inverse.
 
@@ -418,17 +473,19 @@ def solve(A, b, block_size: int = 128, trans: bool = False, **kw):
     rows, refined in fp64 (never a bare ``inv @ b``): a vector through Engine::solve_rhs, a matrix
     of k columns through Engine::solve_rhs_block, which refines all columns per sweep with one pass
     over each matrix and gives every column the accuracy of the one-vector call.  A CUDA tensor A
-    stays on its GPU (Engine::solve_rhs_device / solve_rhs_block_device); X keeps b's shape."""
+    stays on its GPU (Engine::solve_rhs_device / solve_rhs_block_device); X keeps b's shape.
+    ``bounds``: the solve also computes the error bounds of every column (the block path at any width);
+    the return value is x alone -- use :func:`factor` and ``F.infos`` to read them."""
     is_torch = isinstance(A, torch.Tensor)
     if is_torch and A.is_cuda:
         gj = GaussJordan(block_size=block_size, residual="never", **kw)
-        x, _ = gj.solve_resident(A, b, trans=trans)
+        x, _ = gj.solve_resident(A, b, trans=trans, bounds=bounds)
         return x
     bn = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, dtype=np.float64)
     if bn.ndim in (1, 2):
         a = A.detach().to("cpu", torch.float64).numpy() if is_torch else np.asarray(A, dtype=np.float64)
         gj = GaussJordan(block_size=block_size, residual="never", **kw)
-        rep = gj.run(a.shape[0], input=a, rhs=bn, keep_solution=True, trans=trans)
+        rep = gj.run(a.shape[0], input=a, rhs=bn, keep_solution=True, trans=trans, bounds=bounds)
         if rep["status"] == 1:
             raise SingularMatrixError("singular matrix")
         if rep["status"] != 0:

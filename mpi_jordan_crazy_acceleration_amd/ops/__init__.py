@@ -261,6 +261,57 @@ def panel_rhs_t(P: torch.Tensor, V: torch.Tensor, S: torch.Tensor, n: int, m: in
     return S
 
 
+def panel_abs_rhs(P: torch.Tensor, V: torch.Tensor, Y: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0,
+                  C_in: torch.Tensor = None, colmax: torch.Tensor = None, ncols: int = None,
+                  device=None) -> torch.Tensor:
+    """Y = |C_in| + |P| @ |V| over the columns c < n (Device::panel_abs_rhs), in fp64 whatever P's dtype
+    is (an fp32 element is widened exactly, V is not rounded).  Operands as in panel_rhs: ``P`` this
+    rank's rows of a panel (fp64 / fp32), ``V`` the whole block in natural row order (fp64), ``C_in``
+    fp64 or None (0; may be Y itself), ``colmax`` float64[ncols] or None (max |Y| over the real rows,
+    NaN kept).  Padded local rows of Y get |C_in| (or 0).  ``ncols`` defaults to Y's width (1..64, else
+    an error).  ``device``: the native executor to run on instead of the one of Y's torch device (e.g.
+    ``native.async_host_device()`` for CPU tensors)."""
+    assert V.dtype == Y.dtype == torch.float64 and P.stride(-1) == 1 and V.stride(-1) == 1 and Y.stride(-1) == 1
+    ncols = Y.shape[1] if ncols is None else int(ncols)
+    cp, ldc = 0, 0
+    if C_in is not None:
+        assert C_in.dtype == torch.float64 and C_in.stride(-1) == 1
+        cp, ldc = _p(C_in), C_in.stride(0)
+    if colmax is not None:
+        assert colmax.dtype == torch.float64 and colmax.is_contiguous()
+    (device or device_for(Y)).panel_abs_rhs(_DT[P.dtype], _p(P), P.stride(0), n, m, p, k, _p(V), V.stride(0), ncols,
+                                            cp, ldc, _p(Y), Y.stride(0), 0 if colmax is None else _p(colmax))
+    return Y
+
+
+def panel_abs_rhs_t(P: torch.Tensor, V: torch.Tensor, S: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0,
+                    ncols: int = None, device=None) -> torch.Tensor:
+    """S[c, j] = sum over this rank's real local rows r of |P[r, c]| * |V[grow(r), j]| for c < n
+    (Device::panel_abs_rhs_t): rank ``k``'s term of |P_full|^T |V|, in fp64 whatever P's dtype is.
+    Operands as in panel_rhs_t; rows >= n of ``S`` are not written, rows of ``V`` owned by other ranks
+    are not read.  ``ncols`` defaults to S's width (1..64, else an error); ``device`` as in panel_abs_rhs."""
+    assert V.dtype == S.dtype == torch.float64 and P.stride(-1) == 1 and V.stride(-1) == 1 and S.stride(-1) == 1
+    ncols = S.shape[1] if ncols is None else int(ncols)
+    (device or device_for(S)).panel_abs_rhs_t(_DT[P.dtype], _p(P), P.stride(0), n, m, p, k, _p(V), V.stride(0), ncols,
+                                              _p(S), S.stride(0))
+    return S
+
+
+def bound_terms(R: torch.Tensor, D: torch.Tensor, G: torch.Tensor, berr: torch.Tensor, nz_eps: float, safe1: float,
+                safe2: float, rows: int = None, ncols: int = None, device=None) -> torch.Tensor:
+    """The elementwise step of LAPACK's xGERFS (Device::bound_terms) over fp64 views: G = |R| + nz_eps * D,
+    plus safe1 where D <= safe2; berr[j] = max_r |R| / D, with (|R| + safe1) / (D + safe1) where
+    D <= safe2, NaN kept (written, +0.0 for no rows).  ``G`` may be ``R``.  ``rows`` / ``ncols`` default to
+    G's shape (ncols 1..64, else an error); ``device`` as in panel_abs_rhs."""
+    assert R.dtype == D.dtype == G.dtype == berr.dtype == torch.float64 and berr.is_contiguous()
+    assert R.stride(-1) == 1 and D.stride(-1) == 1 and G.stride(-1) == 1
+    rows = G.shape[0] if rows is None else int(rows)
+    ncols = G.shape[1] if ncols is None else int(ncols)
+    (device or device_for(G)).bound_terms(_p(R), R.stride(0), _p(D), D.stride(0), _p(G), G.stride(0), rows, ncols,
+                                          float(nz_eps), float(safe1), float(safe2), _p(berr))
+    return G
+
+
 def rank_update(X: torch.Tensor, W: torch.Tensor, Z: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0,
                 sign: float = 1.0, w_natural: bool = False, ncols: int = None) -> torch.Tensor:
     """X[r, c] += sign * sum_j W[wrow(r), j] * Z[c, j] over this rank's real local rows r and the columns

@@ -208,13 +208,15 @@ class DistributedGaussJordan:
         return self.engine.solve()
 
     def solve_rhs(self, B: np.ndarray, A_rows: Optional[np.ndarray] = None, gen=None, max_refine: int = -1,
-                  tol: float = 1e-15, trans: bool = False):
+                  tol: float = 1e-15, trans: bool = False, bounds: bool = False):
         """Collective, after solve(): A X = B for the n x k block B (an n-vector counts as k = 1),
         the same full B on every rank, every column refined in fp64 (Engine::solve_rhs_block).  The
         fp64 matrix comes from ``gen`` = (kind, seed) or from ``A_rows``, this rank's rows of A (in
         global_row_ids() order) or the full n x n matrix.  ``trans``: A^T X = B from the same inverse
         (each rank's term of inv(A)^T B over its own rows, summed over the ranks: no transpose of the
-        distributed matrix).  Returns (X with B's shape, one info dict per column), the same on every
+        distributed matrix).  ``bounds``: every info gains ``ferr`` and ``berr``, the forward error bound
+        and the componentwise backward error of its column (RhsResult; the same on every rank).
+        Returns (X with B's shape, one info dict per column), the same on every
         rank."""
         B = np.asarray(B, dtype=np.float64)
         b2 = np.ascontiguousarray(B.reshape(self.n, -1))
@@ -229,8 +231,28 @@ class DistributedGaussJordan:
         else:
             gen = (str(gen[0]), int(gen[1]))
         x, infos, _ = self.engine.solve_rhs_block(b2, gen=gen, rows=rows, max_refine=int(max_refine),
-                                                  tol=float(tol), trans=bool(trans))
+                                                  tol=float(tol), trans=bool(trans), bounds=bool(bounds))
         return x.reshape(B.shape), list(infos)
+
+    def _rows_or_gen(self, A_rows, gen, what: str):
+        if gen is not None:
+            return (str(gen[0]), int(gen[1])), None
+        if A_rows is None:
+            raise ValueError(f"{what} needs A_rows or gen=(kind, seed)")
+        rows = np.asarray(A_rows, dtype=np.float64)
+        if rows.shape == (self.n, self.n) and len(self._rows) != self.n:
+            rows = rows[self._rows]
+        return None, np.ascontiguousarray(rows)
+
+    def cond(self, p=np.inf, A_rows: Optional[np.ndarray] = None, gen=None) -> float:
+        """Collective, after solve(): ||A||_p ||inv(A)||_p for p = 1 or inf (else ValueError), with ||A||
+        from ``gen`` = (kind, seed) or ``A_rows`` (as in solve_rhs) and ||inv(A)|| from the resident
+        inverse (Engine::cond).  The same float on every rank."""
+        if p not in (1, np.inf):
+            raise ValueError("cond: p must be 1 or inf")
+        gen, rows = self._rows_or_gen(A_rows, gen, "cond")
+        c = self.engine.cond(gen=gen, rows=rows)
+        return float(c["a_norm1"] * c["inv_norm1"] if p == 1 else c["a_norminf"] * c["inv_norminf"])
 
     def update(self, U: np.ndarray, V: np.ndarray) -> dict:
         """Collective, after solve(): the resident inverse becomes that of A + U V^T
