@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--lda", type=int, default=0, help="row stride of A^T (default M)")
     ap.add_argument("--ldb", type=int, default=0, help="row stride of B (default N)")
     ap.add_argument("--ldc", type=int, default=0, help="row stride of C (default N; the solver's is the padded order)")
+    ap.add_argument("--c-nt", type=int, default=-1, help="GemmExtra::c_nt (MAIN's launches: 3)")
     a = ap.parse_args()
     M, N, K = a.shape
     C_ = load_native()
@@ -38,6 +39,7 @@ def main():
     At = torch.randn(K, max(a.lda, M), dtype=dt, device="cuda")[:, :M]
     B = torch.randn(K, max(a.ldb, N), dtype=dt, device="cuda")[:, :N]
     C = torch.randn(M, max(a.ldc, N), dtype=dt, device="cuda")[:, :N]
+    kw = {"c_nt": a.c_nt}
     err = None
     if a.check:
         C0 = C.clone()
@@ -45,15 +47,15 @@ def main():
         ref = C0.double() + At.double().t() @ B.double()
         err = float((C.double() - ref).abs().max() / ref.abs().max())
         del C0, ref
-    ops.gemm(At, B, C, op=a.op, a_kmajor=True)
+    ops.gemm(At, B, C, op=a.op, a_kmajor=True, **kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.reps):
-        ops.gemm(At, B, C, op=a.op, a_kmajor=True)
+        ops.gemm(At, B, C, op=a.op, a_kmajor=True, **kw)
     torch.cuda.synchronize()
     dt_s = (time.perf_counter() - t0) / a.reps
     print(json.dumps({"M": M, "N": N, "K": K, "dtype": a.dtype, "variant": a.variant or "default", "op": a.op,
-                      "lda": At.stride(0), "ldb": B.stride(0), "ldc": C.stride(0),
+                      "lda": At.stride(0), "ldb": B.stride(0), "ldc": C.stride(0), "c_nt": a.c_nt,
                       "ms": round(dt_s * 1e3, 4), "tflops": round(2.0 * M * N * K / dt_s / 1e12, 2), "rel_err": err}), flush=True)
 
 

@@ -425,6 +425,7 @@ class Engine : private EnginePanels, private EngineWork {
     bool chunk_skip = false;      // one chunk-pass launch per step around the panel columns (chunk_skip_)
     int first_depth = 0;          // steps of the first panel (f_)
     int main_cnt = 0;             // MAIN's C tile non-temporal: loads (1) / stores (2) (main_cnt_)
+    int gemm_phase = 0;           // MAIN's tiles ordered by wave priority: no variant kept (profiles/gemm_phase.md)
   };
   Policy policy() const;
   const std::string& bcast_algo() const { return bcast_algo_; }  // "ring" | "direct"

@@ -552,6 +552,15 @@ __device__ __forceinline__ void wait_pieces(int n) {
 // slice, if any, takes the masked issue), and each DMA piece is one per-lane offset fixed for the
 // whole launch plus the slice's byte offset in an SGPR (soffset): no per-slice VALU address or mask
 // arithmetic, and a constant vmcnt per slice.
+//
+// Tile-uniform fast path: a full tile (Mt = BM, Nt = BN, no row-block selection, no C_in) that every
+// input mask covers entirely or not at all -- each zero-row range, the zero columns, the -C^T column
+// bound -- is classified with scalar code and then loads and stores C with no per-element compare or
+// select: one per-lane offset for the launch, the row in the SGPR offset, the column group a
+// constant; a tile inside a zero row or zero column issues no C load at all.  MAIN's trailing
+// update sees nothing else (pivot block rows, panel columns and chunk bounds are multiples of the
+// tile).  Every other tile takes the masked code; the K loop is shared, so the bits are the same
+// (profiles/gemm_phase.md).
 template <int MODE, int NS, int OCC, int BK, int PEEL = 0, int BNT = glds::BN>
 __global__ __launch_bounds__(glds::NT, OCC) void gemm_glds_f64(GemmArgs g) {
   using namespace glds;
@@ -610,8 +619,22 @@ __global__ __launch_bounds__(glds::NT, OCC) void gemm_glds_f64(GemmArgs g) {
   const int ldi = g.cin ? (int)g.ldcin : ldc;
   const __amdgpu_buffer_rsrc_t rci = g.cin ? rsrc(static_cast<const double*>(g.cin) + m0 * g.ldcin + n0) : rc;
   const int civoff = (rlane * ldi + clane) * ES;
-  // the accumulator input: C itself, or GemmExtra::c_in (ld ldcin); masked elements as 0
-  auto load_c = [&]() {
+  // tile-uniform classification (scalar): uni = the fast path takes the tile, zin = it enters as 0
+  bool uni = Mt == BM && Nt == BN && g.cin == nullptr && g.rsel_m == 0;
+  bool zin = MODE != MODE_ACC;
+  if (MODE == MODE_ACC) {
+    uni = uni && (z1 <= z0 || (z0 == 0 && z1 == BN));
+    zin = z1 > z0;
+#pragma unroll
+    for (int z = 0; z < GemmExtra::kMaxZeroRows; ++z) {
+      const int h = zr1[z] - zr0[z];
+      uni = uni && (h <= 0 || h == BM);
+      zin = zin || h > 0;
+    }
+  }
+  if (g.tneg) uni = uni && (n0 >= g.tncols || n0 + BN <= g.tncols);
+  // the general accumulator input: C itself, or GemmExtra::c_in (ld ldcin); masked elements as 0
+  auto load_c_masked = [&]() {
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -632,6 +655,33 @@ __global__ __launch_bounds__(glds::NT, OCC) void gemm_glds_f64(GemmArgs g) {
           }
         }
       }
+  };
+  // a uniform tile's: all of it or none of it, the cache policy picked once
+  auto load_c_uniform = [&](auto nt_c) {
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int soff = (i * 16 + MF::rq(q)) * ldc * ES;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[i][j][q] = bload_c(rc, cvoff + j * 16 * ES, soff, decltype(nt_c)::value);
+      }
+  };
+  auto load_c = [&]() {
+    if (!uni) {
+      load_c_masked();
+    } else if (zin) {
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) acc[i][j][q] = 0.0;
+    } else if (g.c_nt & 1) {
+      load_c_uniform(std::true_type{});
+    } else {
+      load_c_uniform(std::false_type{});
+    }
   };
   // g.c_overlap: the C loads go out right behind the first slices' LDS-DMA pieces and the first
   // wait covers both (one memory latency at the tile's start instead of two); otherwise C lands
@@ -778,6 +828,33 @@ __global__ __launch_bounds__(glds::NT, OCC) void gemm_glds_f64(GemmArgs g) {
     }
   }
 
+  if (uni) {  // a uniform tile: unmasked stores (the whole tile is inside M x N and inside or outside -C^T)
+    auto store_c_uniform = [&](auto nt_c) {
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int soff = (i * 16 + MF::rq(q)) * ldc * ES;
+#pragma unroll
+          for (int j = 0; j < NJ; ++j) bstore_c(acc[i][j][q], rc, cvoff + j * 16 * ES, soff, decltype(nt_c)::value);
+        }
+    };
+    if (g.c_nt & 2) store_c_uniform(std::true_type{});
+    else store_c_uniform(std::false_type{});
+    if (g.tneg && n0 < g.tncols) {
+      __amdgpu_buffer_rsrc_t rt = rsrc(static_cast<double*>(g.tneg) + n0 * g.ldt + m0);
+      const int ldt = (int)g.ldt;
+      const int tvoff = (clane * ldt + rlane) * ES;
+#pragma unroll
+      for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j)
+            bstore(-acc[i][j][q], rt, tvoff + (i * 16 + MF::rq(q)) * ES, j * 16 * ldt * ES);
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < MI; ++i)
 #pragma unroll

@@ -1057,6 +1057,7 @@ PYBIND11_MODULE(_C, mod) {
                                d["chunk_skip"] = pl.chunk_skip;
                                d["first_depth"] = pl.first_depth;
                                d["main_cnt"] = pl.main_cnt;
+                               d["gemm_phase"] = pl.gemm_phase;
                                d["bcast"] = e.eng->bcast_algo();
                                d["bcast_tuning"] = e.comm->bcast_report();
                                d["comm"] = e.comm->describe();
