@@ -14,6 +14,7 @@
 //           columns of P (W column fragments) and NF = 1 | 2 | 4 fragments of 16 columns of V
 //           (v_mfma_{f64,f32}_16x16x4), walks its slice of the rows and stores the partial product,
 //           widened to fp64, to part[slice][column of P][column of V]
+//           (skinny_cols_kernel with PlainArith, skinny_stream.hpp)
 //   pass 2  S = sum_{slice} part in slice order (+0.0 for an inactive column)
 //
 // The reduction dimension is the local rows, so a small panel has few column tiles and the rows are
@@ -30,130 +31,12 @@
 #include <cstdint>
 
 #include "kernels.hpp"
-#include "skinny.hpp"
+#include "skinny_stream.hpp"
 
 namespace gj {
 namespace kern {
 
 namespace {
-
-// LDS row padding of V (elements) at column width kw: the 4 K lanes of a B-fragment read sit on
-// consecutive rows.  fp64: pitch = 16 (mod 32) elements, 128 (mod 256) bytes apart; fp32: pitch = 16
-// (mod 64) elements, 64 (mod 256) bytes apart.
-template <typename T>
-constexpr int rt_lds_pad(int kw) {
-  return kw == 16 ? 0 : (sizeof(T) == 4 && kw == 32) ? 48 : 16;
-}
-
-// Pass 1.  W = elements each lane loads per row (1: element loads, any alignment; SkinnyMfma<T>::W: one
-// 16-byte load, rows 16-byte aligned).  A K step covers 4 local rows: lane (i = lane % 16,
-// g = lane / 16) holds P[row + g][c0 + i W + j], j < W, and the j-th MFMA of the step produces the
-// output rows {c0 + i W + j : i < 16} -- W interleaved column fragments from one load.
-//
-// V goes through LDS in chunks of kRtKC local rows, picked by the row map and converted to T once
-// per workgroup (every wave of a workgroup needs the same rows of V).  Two buffers, one barrier per
-// chunk: chunk c + 1 is fetched into registers before chunk c is multiplied and written to the other
-// buffer after it.  `real` = this rank's real local rows (global row < n), a prefix of its rows.
-template <typename T, int NF, int W>
-__global__ __launch_bounds__(64 * kRtWaves) void panel_rhs_t_kernel(
-    const T* __restrict__ P, int64_t ldp, int64_t real, int64_t n, uint32_t m, int64_t p, int64_t rk,
-    const double* __restrict__ V, int64_t ldv, int k, const int32_t* __restrict__ active,
-    double* __restrict__ part, int64_t cols_pad, int64_t rchunk) {
-  using MF = SkinnyMfma<T>;
-  constexpr int KW = 16 * NF;
-  constexpr int NT = 64 * kRtWaves;
-  constexpr int LDK = KW + rt_lds_pad<T>(KW);  // LDS row pitch (elements)
-  constexpr int VPT = kRtKC * KW / NT;       // elements of a V chunk per thread (column fixed)
-  constexpr int STEPS = kRtKC / 4;           // K steps per chunk
-  static_assert(NT % KW == 0 && (kRtKC * KW) % NT == 0 && kRtKC % 4 == 0, "chunk shape");
-  __shared__ T vs[2][kRtKC][LDK];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int i = lane & 15, g = lane >> 4;
-
-  const int64_t cbase = ((int64_t)blockIdx.x * kRtWaves + wave) * (16 * W);  // this wave's columns of P
-  const int64_t c0 = cbase + i * W;                                          // this lane's
-  const bool cvec = c0 + W <= n;
-  const int64_t rbeg = (int64_t)blockIdx.y * rchunk;
-  const int64_t rend = rbeg + rchunk < real ? rbeg + rchunk : real;
-
-  // staging: this thread's column of V and its rows of a chunk (row vr0 + q * (NT / KW))
-  const int vc = threadIdx.x % KW, vr0 = threadIdx.x / KW;
-  const bool vcv = vc < k && (!active || active[vc] != 0);
-  double vreg[VPT];
-  auto fetch = [&](int64_t rb) {
-#pragma unroll
-    for (int q = 0; q < VPT; ++q) {
-      const int64_t r = rb + vr0 + q * (NT / KW);
-      double v = 0.0;
-      if (vcv && r < rend) {
-        const uint32_t b = (uint32_t)r / m, e = (uint32_t)r - b * m;  // local rows < 2^31
-        v = V[(((int64_t)b * p + rk) * m + e) * ldv + vc];
-      }
-      vreg[q] = v;
-    }
-  };
-  auto stage = [&](int buf) {
-#pragma unroll
-    for (int q = 0; q < VPT; ++q) vs[buf][vr0 + q * (NT / KW)][vc] = (T)vreg[q];
-  };
-
-  typename MF::acc_t acc[W][NF];
-#pragma unroll
-  for (int j = 0; j < W; ++j)
-#pragma unroll
-    for (int nf = 0; nf < NF; ++nf) acc[j][nf] = typename MF::acc_t{0, 0, 0, 0};
-
-  fetch(rbeg);
-  stage(0);
-  __syncthreads();
-  int buf = 0;
-  for (int64_t rb = rbeg; rb < rend; rb += kRtKC, buf ^= 1) {
-    const bool more = rb + kRtKC < rend;  // uniform over the workgroup
-    if (more) fetch(rb + kRtKC);
-    T a[STEPS][W];
-#pragma unroll
-    for (int st = 0; st < STEPS; ++st) {
-      const int64_t r = rb + st * 4 + g;
-      const T* src = P + r * ldp + c0;
-      if (W > 1 && cvec && r < rend) {
-        const typename MF::vec_t v = *reinterpret_cast<const typename MF::vec_t*>(src);
-#pragma unroll
-        for (int j = 0; j < W; ++j) a[st][j] = v[j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < W; ++j) a[st][j] = (r < rend && c0 + j < n) ? src[j] : T(0);
-      }
-    }
-#pragma unroll
-    for (int st = 0; st < STEPS; ++st) {
-      T b[NF];
-#pragma unroll
-      for (int nf = 0; nf < NF; ++nf) b[nf] = vs[buf][st * 4 + g][nf * 16 + i];
-#pragma unroll
-      for (int j = 0; j < W; ++j)
-#pragma unroll
-        for (int nf = 0; nf < NF; ++nf) acc[j][nf] = MF::op(a[st][j], b[nf], acc[j][nf]);
-    }
-    if (more) stage(buf ^ 1);
-    __syncthreads();
-  }
-
-  // partial product of this row slice, widened: cols_pad is a whole number of tiles, no mask
-  double* out = part + ((int64_t)blockIdx.y * cols_pad + cbase) * KW;
-#pragma unroll
-  for (int j = 0; j < W; ++j)
-#pragma unroll
-    for (int nf = 0; nf < NF; ++nf)
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        out[(int64_t)(MF::row(lane, q) * W + j) * KW + nf * 16 + i] = (double)acc[j][nf][q];
-}
-
-// colmax of the active columns starts from 0 (the integer key of +0.0)
-__global__ void axpy_cols_init_kernel(unsigned long long* colmax, int k, const int32_t* __restrict__ active) {
-  const int j = threadIdx.x;
-  if (j < k && (!active || active[j] != 0)) colmax[j] = 0ull;
-}
 
 // out[c] = sum over the real local rows of |X[r][c]|: a workgroup covers 64 columns, its 4 row
 // groups walk the rows 4 apart and are summed in a fixed order.
@@ -169,18 +52,6 @@ __global__ __launch_bounds__(256) void col_abs_sum_kernel(const T* __restrict__ 
   sh[rs][cl] = sum;
   __syncthreads();
   if (rs == 0 && c < n) out[c] = ((sh[0][cl] + sh[1][cl]) + sh[2][cl]) + sh[3][cl];
-}
-
-template <typename T, int NF>
-void launch_rt(const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int k,
-               const int32_t* active, double* part, const RtPlan& pl, hipStream_t s) {
-  const dim3 grid((unsigned)pl.tiles, (unsigned)pl.S), block(64 * kRtWaves);
-  if (pl.vec)
-    hipLaunchKernelGGL((panel_rhs_t_kernel<T, NF, SkinnyMfma<T>::W>), grid, block, 0, s, static_cast<const T*>(P), ldp,
-                       pl.real, L.n, (uint32_t)L.m, L.p, L.k, V, ldv, k, active, part, pl.cols_pad, pl.rchunk);
-  else
-    hipLaunchKernelGGL((panel_rhs_t_kernel<T, NF, 1>), grid, block, 0, s, static_cast<const T*>(P), ldp, pl.real,
-                       L.n, (uint32_t)L.m, L.p, L.k, V, ldv, k, active, part, pl.cols_pad, pl.rchunk);
 }
 
 }  // namespace
@@ -201,9 +72,7 @@ void panel_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const do
   set_probe_name<struct RhsTProbe>(g_last_rhs_t_kernel, "rhst%d:%s:%s:s%d", padded_kw(k),
                                    dt == DType::F64 ? "f64" : "f32", pl.vec ? "vec" : "scalar", pl.S);
   with_kw(k, [&](auto KW) {
-    constexpr int NF = KW / 16;
-    if (dt == DType::F64) launch_rt<double, NF>(P, ldp, L, V, ldv, (int)k, active, part, pl, s);
-    else launch_rt<float, NF>(P, ldp, L, V, ldv, (int)k, active, part, pl, s);
+    launch_skinny_cols<PlainArith, KW>(dt, P, ldp, L, V, ldv, (int)k, active, part, pl, s);
     launch_rt_reduce<KW>(part, pl, L, (int)k, S, lds, active, s);
   });
 }
@@ -212,7 +81,7 @@ void panel_rhs_t(DType dt, const void* P, int64_t ldp, const Layout& L, const do
 void axpy_cols_masked(double* Y, int64_t ldy, const double* C_in, int64_t ldc, const double* S, int64_t lds,
                       double sign, int64_t rows, int64_t k, const int32_t* active, double* colmax, hipStream_t s) {
   unsigned long long* cm = reinterpret_cast<unsigned long long*>(colmax);
-  if (cm) hipLaunchKernelGGL(axpy_cols_init_kernel, dim3(1), dim3(64), 0, s, cm, (int)k, active);
+  if (cm) launch_zero_keys(cm, (int)k, active, s);
   if (rows <= 0) return;
   with_kw(k, [&](auto KW) {
     launch_col_epilogue<KW>(DenseTerm{S, lds}, C_in, ldc, Y, ldy, sign, rows, (int)k, active, cm, s);

@@ -229,21 +229,16 @@ void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* 
                  const double* Z, int64_t ldz, int64_t k, double sign, hipStream_t s) {
   const int64_t es = (int64_t)dtype_size(dt);
   // a tile's rows are addressed from the tile's base with 32-bit byte offsets
-  if (ldx < 0 || ldx > ((int64_t(1) << 31) / es - kRkuTileN) / (kRkuTileM - 1))
-    throw Error(Status::BadArgs, "rank_update: leading dimension too large for 32-bit tile offsets");
+  check_ld_32bit("rank_update", ldx, es, kRkuTileM, kRkuTileN);
   const int64_t real = L.real_rows();
   // 16-byte pieces of X need 16-byte aligned rows; a lane's columns start on a multiple of the width
   const bool vec = rows_16B_aligned(X, ldx, (size_t)es);
   set_probe_name<struct RkuProbe>(g_last_rank_update_kernel, "rku%d:%s:%s", (int)((k + 3) / 4 * 4),
                                   dt == DType::F64 ? "f64" : "f32", vec ? "vec" : "scalar");
   if (real <= 0 || L.n <= 0) return;
-  if (dt == DType::F64) {
-    if (vec) launch_rku_k<double, 2>(X, ldx, real, L, W, ldw, w_natural, Z, ldz, (int)k, sign, s);
-    else launch_rku_k<double, 1>(X, ldx, real, L, W, ldw, w_natural, Z, ldz, (int)k, sign, s);
-  } else {
-    if (vec) launch_rku_k<float, 4>(X, ldx, real, L, W, ldw, w_natural, Z, ldz, (int)k, sign, s);
-    else launch_rku_k<float, 1>(X, ldx, real, L, W, ldw, w_natural, Z, ldz, (int)k, sign, s);
-  }
+  with_panel(dt, vec, [&](auto zero, auto VW) {
+    launch_rku_k<decltype(zero), VW>(X, ldx, real, L, W, ldw, w_natural, Z, ldz, (int)k, sign, s);
+  });
 }
 
 }  // namespace kern

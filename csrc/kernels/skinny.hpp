@@ -1,8 +1,8 @@
 // Shared pieces of the skinny-block kernels (panel_rhs.hip, panel_rhs_t.hip, panel_abs.hip,
 // rank_update.hip): a tall panel against a skinny fp64 block of at most 64 columns.  The MFMA traits,
-// the NaN-keeping magnitude key, the host-side launch helpers, the split plans of the two streaming
-// products, the column epilogue Y = C_in + sign * term with its column maxima and the slice sum of
-// the transposed products.
+// the NaN-keeping magnitude key and its reductions, the host-side launch helpers, the split plans of
+// the two streaming products (their pass 1 is skinny_stream.hpp), the column epilogue
+// Y = C_in + sign * term with its column maxima and the slice sum of the transposed products.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <string>
 #include <type_traits>
 
 #include "gj/common.hpp"
@@ -19,15 +20,15 @@
 namespace gj {
 namespace kern {
 
-// v_mfma_{f64,f32}_16x16x4: the accumulator, the 16-byte load of T and the row of accumulator
-// element q.  The LDS padding is the choice of each kernel and stays with it.
+// v_mfma_{f64,f32}_16x16x4: the operand, the accumulator, the 16-byte piece of T and the row of
+// accumulator element q.  The LDS padding is the choice of each kernel and stays with it.
 template <typename T>
 struct SkinnyMfma;
 template <>
 struct SkinnyMfma<double> {
+  typedef double elem_t;
   typedef double acc_t __attribute__((ext_vector_type(4)));
   typedef double vec_t __attribute__((ext_vector_type(2)));
-  static constexpr int W = 2;  // elements of a 16-byte load
   static __device__ __forceinline__ acc_t op(double a, double b, acc_t c) {
     return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
   }
@@ -35,9 +36,9 @@ struct SkinnyMfma<double> {
 };
 template <>
 struct SkinnyMfma<float> {
+  typedef float elem_t;
   typedef float acc_t __attribute__((ext_vector_type(4)));
   typedef float vec_t __attribute__((ext_vector_type(4)));
-  static constexpr int W = 4;
   static __device__ __forceinline__ acc_t op(float a, float b, acc_t c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
   }
@@ -71,6 +72,13 @@ inline bool rows_16B_aligned(const void* ptr, int64_t ld, size_t elem_size) {
   return reinterpret_cast<uintptr_t>(ptr) % 16 == 0 && ((size_t)ld * elem_size) % 16 == 0;
 }
 
+// Refuses (Status::BadArgs) a leading dimension ld of elements of es bytes where the byte offset of a
+// tile's last row (row rows - 1, `cols` columns in) from the tile's base would not fit 32 bits
+inline void check_ld_32bit(const char* op, int64_t ld, int64_t es, int rows, int cols = 0) {
+  if (ld < 0 || ld > ((int64_t(1) << 31) / es - cols) / (rows - 1))
+    throw Error(Status::BadArgs, std::string(op) + ": leading dimension too large for 32-bit tile offsets");
+}
+
 // k <= 64 columns -> the compile-time column width the kernels are built for: f(KW) with KW an
 // integral_constant of 16, 32 or 64
 template <typename F>
@@ -82,9 +90,47 @@ inline auto with_kw(int64_t k, F&& f) {
 inline int padded_kw(int64_t k) {
   return with_kw(k, [](auto KW) -> int { return KW; });
 }
+// a panel's dtype x (16-byte pieces | elements) -> f(T(0), W): T the element type, W an
+// integral_constant of the elements of T a lane moves at once (16 / sizeof(T), or 1)
+template <typename F>
+inline void with_panel(DType dt, bool vec, F&& f) {
+  if (dt == DType::F64) {
+    if (vec) f(0.0, std::integral_constant<int, 2>{});
+    else f(0.0, std::integral_constant<int, 1>{});
+  } else {
+    if (vec) f(0.0f, std::integral_constant<int, 4>{});
+    else f(0.0f, std::integral_constant<int, 1>{});
+  }
+}
+
+// The keys of the columns j < k that are active start from 0, the key of +0.0 (one workgroup)
+static __global__ void zero_keys_kernel(unsigned long long* keys, int k, const int32_t* __restrict__ active) {
+  const int j = threadIdx.x;
+  if (j < k && (!active || active[j] != 0)) keys[j] = 0ull;
+}
+inline void launch_zero_keys(unsigned long long* keys, int k, const int32_t* active, hipStream_t s) {
+  hipLaunchKernelGGL(zero_keys_kernel, dim3(1), dim3(64), 0, s, keys, k, active);
+}
+
+// The maximum of a workgroup's keys per column into out[c], for a workgroup of 256 threads laid out
+// as thread = column tid % KW, row group tid / KW; `on` = this thread's column takes part.  Every
+// thread of the workgroup calls it.
+template <int KW>
+__device__ __forceinline__ void block_key_max(unsigned long long key, bool on, unsigned long long* out) {
+  constexpr int RG = 256 / KW;
+  const int c = threadIdx.x % KW, rs = threadIdx.x / KW;
+  __shared__ unsigned long long sh[256];
+  sh[threadIdx.x] = key;
+  __syncthreads();
+  if (rs == 0 && on) {
+#pragma unroll
+    for (int q = 1; q < RG; ++q) key = sh[q * KW + c] > key ? sh[q * KW + c] : key;
+    atomicMax(out + c, key);  // an integer maximum: the same bits in any order
+  }
+}
 
 // The shapes and split plans of the two streaming products, shared by each product and its sibling
-// of absolute values (panel_rhs.hip / panel_rhs_t.hip / panel_abs.hip).
+// of absolute values (skinny_stream.hpp).
 constexpr int kRhsMI = 2;                             // 16-row fragments per wave
 constexpr int kRhsWaves = 4;                          // waves per workgroup
 constexpr int kRhsTileM = 16 * kRhsMI * kRhsWaves;    // 128 rows per workgroup
@@ -211,15 +257,7 @@ __global__ __launch_bounds__(256) void col_epilogue_kernel(Src src, const double
       }
       Y[r * ldy + c] = y;
     }
-  if (!colmax) return;
-  __shared__ unsigned long long sh[256];
-  sh[threadIdx.x] = key;
-  __syncthreads();
-  if (rs == 0 && on) {
-#pragma unroll
-    for (int q = 1; q < RG; ++q) key = sh[q * KW + c] > key ? sh[q * KW + c] : key;
-    atomicMax(colmax + c, key);  // an integer maximum: the same bits in any order
-  }
+  if (colmax) block_key_max<KW>(key, on, colmax);  // uniform
 }
 
 template <int KW, typename Src, bool AbsC = false>
