@@ -10,8 +10,10 @@
 // Every op takes a stream role (S_MAIN/S_SIDE/S_COMM); the host device executes synchronously.
 #pragma once
 
+#include <atomic>
 #include <cmath>
 #include <limits>
+#include <map>
 #include <memory>
 #include <string>
 
@@ -134,6 +136,19 @@ struct PieceMove {
 // Device::gemm / gemm_batch ran ("host" on the host executor, the HIP names in kernels/gemm.hip).
 // Written at every launch site, read by nothing but tests: no effect on dispatch, no device work.
 inline thread_local const char* g_last_gemm_kernel = "";
+// Test probe: a census of those names over every thread of the process (name -> launches), for what a
+// whole solve ran on each of its streams and ranks.  Off by default: a launch site then pays one
+// relaxed load.  gemm_census_enable(true) clears the counts and starts counting, (false) stops and
+// keeps them for gemm_census_counts().  (runtime/host_device.cpp)
+extern std::atomic<bool> g_gemm_census_on;
+void gemm_census_enable(bool on);
+void gemm_census_add(const char* name);
+std::map<std::string, int64_t> gemm_census_counts();
+// every launch site names its kernel through this
+inline void note_gemm_kernel(const char* name) {
+  g_last_gemm_kernel = name;
+  if (g_gemm_census_on.load(std::memory_order_relaxed)) gemm_census_add(name);
+}
 
 // One product of a batched small-GEMM launch (Device::gemm_batch): C (+)= A B, A K-major.
 struct GemmDesc {

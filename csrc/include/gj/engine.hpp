@@ -430,6 +430,35 @@ class Engine : private EnginePanels, private EngineWork {
   Policy policy() const;
   const std::string& bcast_algo() const { return bcast_algo_; }  // "ring" | "direct"
 
+  // Every choice the constructor takes from the problem size, as a pure function of the shape: no
+  // device, no communicator, no environment.  plan_policy() gives the depth, the chunk plan and the
+  // CU reservation to ask for; grant() then takes the number of CUs the device really set aside and
+  // fills in the switches that depend on it.  The constructor calls both and applies the GJ_*
+  // overrides afterwards.  GJ_POLICY_LIKE=<n>x<p> (tests only) feeds the planner the layout of an
+  // n x n problem on p ranks (same m and dtype, this rank's index clamped to p - 1) for the automatic
+  // depth, the reservation and the switches, so that a small engine runs a large problem's corner;
+  // the chunk plan, the min(depth, Nr) clamp and every buffer size stay those of the engine's own layout.
+  struct PolicyPlan {
+    int depth = 1;            // steps per panel: min(request or automatic, kMaxDepth, Nr)
+    int reserve_request = 0;  // CUs to ask Device::reserve_cus for
+    std::vector<int64_t> chunk_begin, chunk_end;  // chunk plan (block columns), every panel d steps deep
+    // after grant():
+    int reserve_cus = 0;
+    bool dense_gemm = false;
+    int gemm_tile = 64;
+    bool skip_cols = false, chunk_skip = false, lat_reg = false, lat_wide = false;
+    // what grant() decides from
+    int64_t p = 1, m = 0, npad = 0, max_nblk = 0;
+    void grant(int cus);
+  };
+  // depth_request / chunk_cols_request: 0 = automatic; reserve_request: -1 = automatic
+  static PolicyPlan plan_policy(int64_t n, int64_t m, int p, int rank, DType dtype, bool on_gpu, int depth_request,
+                                int64_t chunk_cols_request, int reserve_request);
+  // The chunk plan: the Nr block columns in runs of about chunk_cols_request columns (0: automatic),
+  // each a multiple of d blocks, the first one f blocks wider when the first panel is shallower (f < d)
+  static void plan_chunks(int64_t Nr, int64_t npad, int64_t m, int d, int f, int64_t chunk_cols_request,
+                          std::vector<int64_t>& chunk_begin, std::vector<int64_t>& chunk_end);
+
  private:
   using EngineWork::kMaxDepth;
   // pinned pivot-result slots: one per step of a panel in flight (the host-free chain of one rank

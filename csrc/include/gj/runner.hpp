@@ -75,6 +75,7 @@ struct RunReport {
   std::vector<double> corner_a, corner_inv;
   std::vector<double> inverse;      // n*n if keep_inverse
   SolveStats stats;                 // rank 0
+  std::vector<Engine::Policy> policy_ranks;  // what every rank's engine chose (Engine::policy)
   std::string device_desc, comm_desc;
   double gflops_nominal = 0;        // 2 n^3 / glob_time / 1e9
   bool rhs_solved = false;

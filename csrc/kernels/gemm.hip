@@ -1050,7 +1050,7 @@ static void launch_lat(const GemmArgs& a0, hipStream_t s) {
   a.tiles_n = (int)((a.N + 31) / 32);
   const int64_t nwg = (int64_t)a.tiles_m * a.tiles_n;
   if (nwg <= 0) return;
-  g_last_gemm_kernel = "lat64";
+  note_gemm_kernel("lat64");
   hipLaunchKernelGGL((gemm_lat_f64<MODE>), dim3((unsigned)nwg), dim3(256), 0, s, a);
 }
 
@@ -1160,7 +1160,7 @@ static void launch_glds(const GemmArgs& a0, hipStream_t s) {
     if (nwg <= 0) return;
     a.group = glds_group();
     a.c_nt = glds_cnt(a.c_nt);
-    g_last_gemm_kernel = build0 == 33 ? "glds64:t128:b33:peel" : build0 == 32 ? "glds64:t128:b32:peel" : "glds64:t128:b23:peel";
+    note_gemm_kernel(build0 == 33 ? "glds64:t128:b33:peel" : build0 == 32 ? "glds64:t128:b32:peel" : "glds64:t128:b23:peel");
     if (build0 == 33)
       hipLaunchKernelGGL((gemm_glds_f64<MODE, 3, 3, 8, 1, 128>), dim3((unsigned)nwg), dim3(glds::NT), 0, s, a);
     else if (build0 == 32)
@@ -1191,11 +1191,11 @@ static void launch_glds(const GemmArgs& a0, hipStream_t s) {
   const int forced = glds_build_forced();
   const int build = forced ? forced : a.build ? a.build : a.dense ? 25 : glds_peel() ? 33 : 23;
   if (glds_peel())
-    g_last_gemm_kernel = build == 25 ? "glds64:t64:b25:peel" : build == 33 ? "glds64:t64:b33:peel"
+    note_gemm_kernel(build == 25 ? "glds64:t64:b25:peel" : build == 33 ? "glds64:t64:b33:peel"
                          : build == 43 ? "glds64:t64:b43:peel" : build == 1623 ? "glds64:t64:b1623:peel"
-                                                                                : "glds64:t64:b23:peel";
+                                                                                : "glds64:t64:b23:peel");
   else
-    g_last_gemm_kernel = build == 25 ? "glds64:t64:b25" : build == 33 ? "glds64:t64:b33" : "glds64:t64:b23";
+    note_gemm_kernel(build == 25 ? "glds64:t64:b25" : build == 33 ? "glds64:t64:b33" : "glds64:t64:b23");
   if (glds_peel()) {
     if (build == 25)
       hipLaunchKernelGGL((gemm_glds_f64<MODE, 2, 5, 8, 1>), dim3((unsigned)nwg), dim3(glds::NT), 0, s, a);
@@ -1469,7 +1469,7 @@ static void launch_glds32(const GemmArgs& a0, hipStream_t s) {
     if (nwg <= 0) return;
     a.group = 4;
     a.c_nt = glds_cnt(a.c_nt);
-    g_last_gemm_kernel = "glds32:t256";
+    note_gemm_kernel("glds32:t256");
     hipLaunchKernelGGL((gemm_glds_f32<MODE, 2, 3, 16, 1, 256>), dim3((unsigned)nwg), dim3(glds32::NT), 0, s, a);
     return;
   }
@@ -1492,7 +1492,7 @@ static void launch_glds32(const GemmArgs& a0, hipStream_t s) {
     const std::string v = e ? e : "";
     return v == "2.3" ? 23 : v == "3.3" ? 33 : 24;
   }();
-  g_last_gemm_kernel = "glds32:t128";
+  note_gemm_kernel("glds32:t128");
   if (glds_peel()) {
     if (b32 == 33)
       hipLaunchKernelGGL((gemm_glds_f32<MODE, 3, 3, 16, 1>), dim3((unsigned)nwg), dim3(glds32::NT), 0, s, a);
@@ -1533,7 +1533,7 @@ static void check_cfg(const GemmArgs& a) {
 template <typename T, int AL, int MODE, typename CF>
 static void launch_cfg(const GemmArgs& a0, hipStream_t s) {
   check_cfg<T, AL, MODE, CF>(a0);
-  g_last_gemm_kernel = CfgName<CF>::v;
+  note_gemm_kernel(CfgName<CF>::v);
   GemmArgs a = a0;
   a.tiles_m = (int)((a.M + CF::BM - 1) / CF::BM);
   a.tiles_n = (int)((a.N + CF::BN - 1) / CF::BN);
@@ -1735,7 +1735,7 @@ void gemm_batch(DType dt, const GemmDesc* d, int n, hipStream_t s) {
       else check_cfg<float, 1, MODE_ACC, CF>(t);
     }
   }
-  g_last_gemm_kernel = lat ? "batch:lat" : "batch:small";
+  note_gemm_kernel(lat ? "batch:lat" : "batch:small");
   const int64_t TBM = lat ? 128 : CF::BM, TBN = lat ? 32 : CF::BN;
   GemmBatch b{};
   int tiles = 0;

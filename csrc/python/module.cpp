@@ -191,6 +191,33 @@ static py::dict rhs_info(const RhsResult& rr, bool bounds = false) {
   return info;
 }
 
+// Engine::Policy as Engine.policy and run_local's policy_ranks show it (the engine adds bcast,
+// bcast_tuning and comm)
+static py::dict policy_to_dict(const Engine::Policy& pl) {
+  py::dict d;
+  d["depth"] = pl.depth;
+  d["chunk_cols"] = pl.chunk_cols;
+  d["nchunks"] = pl.nchunks;
+  d["reserve_cus"] = pl.reserve_cus;
+  d["block_inverse"] = pl.block_inverse;
+  d["comm_small_tiles"] = pl.comm_small_tiles;
+  d["dense_gemm"] = pl.dense_gemm;
+  d["look_ahead_rows"] = pl.la_side ? "SIDE" : "COMM";
+  d["pivot"] = pl.pivot;
+  if (!pl.fault_injection.empty()) d["fault_injection"] = pl.fault_injection;
+  d["env_overrides"] = pl.env_overrides;
+  d["gemm_tile"] = pl.gemm_tile;
+  d["split"] = pl.split;
+  d["lat_wide"] = pl.lat_wide;
+  d["skip_cols"] = pl.skip_cols;
+  d["lat_reg"] = pl.lat_reg;
+  d["chunk_skip"] = pl.chunk_skip;
+  d["first_depth"] = pl.first_depth;
+  d["main_cnt"] = pl.main_cnt;
+  d["gemm_phase"] = pl.gemm_phase;
+  return d;
+}
+
 // max_refine < 0: the default budget of refinement steps, by the engine dtype
 static int refine_budget(const Engine& eng, int max_refine) {
   return max_refine >= 0 ? max_refine : eng.options().dtype == DType::F64 ? 2 : 10;
@@ -257,6 +284,41 @@ PYBIND11_MODULE(_C, mod) {
   mod.def("last_gemm_kernel", [] { return std::string(kern::last_gemm_kernel()); },
           "test probe: family / build name of the kernel this thread's last Device.gemm / gemm_batch ran "
           "('host' on the host executor)");
+  mod.def("gemm_census", [](bool on) { gemm_census_enable(on); },
+          "test probe: count every Device.gemm / gemm_batch launch of the process by its last_gemm_kernel name; True "
+          "clears the counts and starts, False stops and keeps them (off by default)");
+  mod.def("gemm_census_counts", [] { return gemm_census_counts(); }, "the census: {kernel name: launches}");
+  mod.def("plan_policy",
+          [](int64_t n, int64_t m, int p, int rank, const std::string& dtype, bool on_gpu, int depth,
+             int64_t chunk_cols, int reserve_cus, int granted_cus) {
+            Engine::PolicyPlan pl =
+                Engine::plan_policy(n, m, p, rank, parse_dtype(dtype), on_gpu, depth, chunk_cols, reserve_cus);
+            pl.grant(granted_cus >= 0 ? granted_cus : pl.reserve_request);
+            py::dict d;
+            d["depth"] = pl.depth;
+            d["first_depth"] = pl.depth;
+            d["nchunks"] = (int)pl.chunk_begin.size();
+            int64_t w = 0;
+            for (size_t c = 0; c < pl.chunk_begin.size(); ++c) w = std::max(w, (pl.chunk_end[c] - pl.chunk_begin[c]) * m);
+            d["chunk_cols"] = w;
+            d["chunk_begin"] = pl.chunk_begin;
+            d["chunk_end"] = pl.chunk_end;
+            d["reserve_request"] = pl.reserve_request;
+            d["reserve_cus"] = pl.reserve_cus;
+            d["dense_gemm"] = pl.dense_gemm;
+            d["gemm_tile"] = pl.gemm_tile;
+            d["skip_cols"] = pl.skip_cols;
+            d["chunk_skip"] = pl.chunk_skip;
+            d["lat_reg"] = pl.lat_reg;
+            d["lat_wide"] = pl.lat_wide;
+            return d;
+          },
+          py::arg("n"), py::arg("m"), py::arg("p") = 1, py::arg("rank") = 0, py::arg("dtype") = "fp64",
+          py::arg("on_gpu") = true, py::arg("depth") = 0, py::arg("chunk_cols") = 0, py::arg("reserve_cus") = -1,
+          py::arg("granted_cus") = -1,
+          "Engine::plan_policy: what an engine of this shape chooses with no GJ_* override, under Engine.policy's "
+          "keys (plus chunk_begin / chunk_end in block columns and reserve_request); granted_cus: the CUs the "
+          "device sets aside, -1 = all that are asked for.  No device is touched.");
   mod.def("set_rhs_splitk", [](int s) { kern::set_rhs_splitk(s); },
           "test hook: K-split of the following Device.panel_rhs launches on the GPU (0 = auto, s >= 1 forces s)");
   mod.def("last_rhs_kernel", [] { return std::string(kern::last_rhs_kernel()); },
@@ -1036,28 +1098,7 @@ PYBIND11_MODULE(_C, mod) {
                              })
       .def_property_readonly("policy",
                              [](PyEngine& e) {
-                               const Engine::Policy pl = e.eng->policy();
-                               py::dict d;
-                               d["depth"] = pl.depth;
-                               d["chunk_cols"] = pl.chunk_cols;
-                               d["nchunks"] = pl.nchunks;
-                               d["reserve_cus"] = pl.reserve_cus;
-                               d["block_inverse"] = pl.block_inverse;
-                               d["comm_small_tiles"] = pl.comm_small_tiles;
-                               d["dense_gemm"] = pl.dense_gemm;
-                               d["look_ahead_rows"] = pl.la_side ? "SIDE" : "COMM";
-                               d["pivot"] = pl.pivot;
-                               if (!pl.fault_injection.empty()) d["fault_injection"] = pl.fault_injection;
-                               d["env_overrides"] = pl.env_overrides;
-                               d["gemm_tile"] = pl.gemm_tile;
-                               d["split"] = pl.split;
-                               d["lat_wide"] = pl.lat_wide;
-                               d["skip_cols"] = pl.skip_cols;
-                               d["lat_reg"] = pl.lat_reg;
-                               d["chunk_skip"] = pl.chunk_skip;
-                               d["first_depth"] = pl.first_depth;
-                               d["main_cnt"] = pl.main_cnt;
-                               d["gemm_phase"] = pl.gemm_phase;
+                               py::dict d = policy_to_dict(e.eng->policy());
                                d["bcast"] = e.eng->bcast_algo();
                                d["bcast_tuning"] = e.comm->bcast_report();
                                d["comm"] = e.comm->describe();
@@ -1468,6 +1509,11 @@ PYBIND11_MODULE(_C, mod) {
     o["corner_inv"] = to_array(r.corner_inv, r.corner_inv.empty() ? 0 : r.nm, r.corner_inv.empty() ? 0 : r.nm);
     if (c.keep_inverse && r.status == Status::Ok) o["inverse"] = to_array(r.inverse, c.n, c.n);
     o["stats"] = stats_to_dict(r.stats);
+    {
+      py::list pr;
+      for (const Engine::Policy& pl : r.policy_ranks) pr.append(policy_to_dict(pl));
+      o["policy_ranks"] = pr;
+    }
     o["device"] = r.device_desc;
     o["comm"] = r.comm_desc;
     o["gflops_nominal"] = r.gflops_nominal;

@@ -13,12 +13,35 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <map>
+#include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
 #include "gj/gen.hpp"
 
 namespace gj {
+
+// GEMM launch census (gj/device.hpp)
+std::atomic<bool> g_gemm_census_on{false};
+namespace {
+std::mutex g_gemm_census_mu;
+std::map<std::string, int64_t> g_gemm_census;
+}  // namespace
+void gemm_census_enable(bool on) {
+  std::lock_guard<std::mutex> lk(g_gemm_census_mu);
+  if (on) g_gemm_census.clear();
+  g_gemm_census_on.store(on, std::memory_order_relaxed);
+}
+void gemm_census_add(const char* name) {
+  std::lock_guard<std::mutex> lk(g_gemm_census_mu);
+  ++g_gemm_census[name];
+}
+std::map<std::string, int64_t> gemm_census_counts() {
+  std::lock_guard<std::mutex> lk(g_gemm_census_mu);
+  return g_gemm_census;
+}
 
 namespace {
 
@@ -468,7 +491,7 @@ void HostDevice::h_block(DType dt, void* R, int64_t ldr, const void* Ht, int64_t
 void HostDevice::gemm(DType dt, GemmOp op, ALayout al, int64_t M, int64_t N, int64_t K,
                       const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                       int, const GemmExtra& ex) {
-  g_last_gemm_kernel = "host";
+  note_gemm_kernel("host");
   if (M <= 0 || N <= 0) return;
   if (dt == DType::F64)
     gemm_t<double>(op, al, M, N, K, tp<double>(A), lda, tp<double>(B), ldb, tp<double>(C), ldc,

@@ -89,6 +89,84 @@ int64_t injected_step(const char* var, int rank) {
 }
 }  // namespace
 
+// ---------------------------------------------------------------- size-selected policy
+// The choices taken from the problem's shape alone (README "Size-selected policies";
+// tests/test_policy_plan.py pins the table).  The measurements behind the switches of grant() that
+// carry no note here are with their GJ_* overrides in the constructor.
+Engine::PolicyPlan Engine::plan_policy(int64_t n, int64_t m, int p, int rank, DType dtype, bool on_gpu,
+                                       int depth_request, int64_t chunk_cols_request, int reserve_request) {
+  GJ_REQUIRE(n > 0 && m > 0 && p > 0 && rank >= 0 && rank < p, "plan_policy: bad shape");
+  (void)dtype;  // no size-selected choice depends on it today: fp32 follows gemm_tile (the 256-wide tile at 128)
+  const Layout L = Layout::make(n, m, p, rank);
+  PolicyPlan pl;
+  pl.p = L.p;
+  pl.m = L.m;
+  pl.npad = L.npad;
+  pl.max_nblk = L.max_nblk;
+  // auto depth: profiles/small_n_sweep.md (N=8192: depth 2 34.6 vs 35.9 ms; N=16384: 4 wins), and
+  // 8 on ranks of <= 4096 rows of a large matrix (p = 8 at N = 32768: K = 1024 halves the panel
+  // boundaries the pivot chain must hide behind a short trailing update; emulated under the
+  // communication-cost model 0.167 vs 0.177 s, while depth 6 / 8 lose at p = 1 / 2 / 4 and at
+  // N = 16384: profiles/depth_pgt1.md)
+  const bool small_rank = L.p > 1 && L.max_nblk * L.m <= 4096;
+  // Depth 2 on p > 1 ranks of <= 2048 rows (p = 8 at N = 16384) is 0.0382 vs 0.0408 s per emulated
+  // rank under the direct 50 GB/s model (profiles/depth_pgt1.md), but it is the configuration of
+  // the round-3 wrong inverse (p = 8, depth 2, async ranks), whose cause is not localised
+  // (profiles/verify_r6.md): p > 1 keeps depth 4 by default; --depth 2 selects it explicitly.
+  // (One GPU at N = 32768, depth 8 with the co-resident candidate inverse: 0.9 % faster on one box,
+  // 0.5-0.8 % slower on another, same-box A/Bs of round 4 -- not adopted, profiles/rocprof_n32768_r4.md.)
+  const int want = depth_request > 0 ? depth_request
+                   : (L.p == 1 && L.npad <= 8192) ? 2
+                   : (small_rank && L.npad > 16384) ? 8 : 4;
+  pl.depth = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)want, (int64_t)kMaxDepth, L.Nr}));
+  plan_chunks(L.Nr, L.npad, m, pl.depth, pl.depth, chunk_cols_request, pl.chunk_begin, pl.chunk_end);
+  // CU reservation, auto: up to N = 16384 the pivot chain is the critical path and its block inverses
+  // only start on a CU no trailing-update workgroup occupies, so keep 32 CUs (1/8 of the chip) off the
+  // MAIN stream -- the first 32 mask bits, i.e. one CU of every shader engine (bits interleave XCCs, then
+  // SEs: bench/cu_mask_probe.hip), since a launch's workgroups are split evenly over the 32 SEs and
+  // an unbalanced mask makes the smallest SE the straggler (profiles/cu_reserve_sweep.md):
+  // N=8192 p=1 -12 %, emulated p=2/4/8 at N=16384 -10/-16/-14 %.  At N=32768 the GEMM is the
+  // critical path and the mask costs 4-10 % (profiles/cu_reserve_sweep.md) -- except on ranks
+  // with <= 4096 rows (p = 8 at N = 32768), where the pivot chain and the RCCL workgroups of its
+  // collectives need the free CUs: under the communication-cost model p = 8 is 6.6 % faster with
+  // the reservation at 100 GB/s, p = 2 / 4 are 9 / 6 % slower (profiles/cu_reserve_pgt1.md).
+  pl.reserve_request = reserve_request >= 0 ? reserve_request : (on_gpu && (L.npad <= 16384 || small_rank)) ? 32 : 0;
+  pl.grant(0);
+  return pl;
+}
+
+void Engine::plan_chunks(int64_t Nr, int64_t npad, int64_t m, int d, int f, int64_t chunk_cols_request,
+                         std::vector<int64_t>& chunk_begin, std::vector<int64_t>& chunk_end) {
+  int64_t target_cols = chunk_cols_request;
+  // 8192 columns: measured 2-4 % faster than 4096 / 16384 in the p = 2, 4, 8 critical-path
+  // emulation at N = 32768 (fewer GEMM tails per panel, still 4 chunks to pipeline the broadcast)
+  if (target_cols <= 0) target_cols = std::max<int64_t>((npad + 7) / 8, std::min<int64_t>(8192, (npad + 1) / 2));
+  int64_t cw = std::max<int64_t>(1, target_cols / m);
+  cw = ((cw + d - 1) / d) * d;
+  // (chunk boundaries sit on panel boundaries: with a shallower first panel, at f + k d -- the
+  // first chunk f blocks wider)
+  chunk_begin.clear();
+  chunk_end.clear();
+  for (int64_t b = 0; b < Nr;) {
+    const int64_t e = std::min(Nr, b == 0 ? cw + (f < d ? f : 0) : b + cw);
+    chunk_begin.push_back(b);
+    chunk_end.push_back(e);
+    b = e;
+  }
+}
+
+void Engine::PolicyPlan::grant(int cus) {
+  reserve_cus = cus;
+  // the 5-per-CU trailing-update build under a reservation, except at N <= 8192 on one rank
+  dense_gemm = cus > 0 && !(p == 1 && npad <= 8192);
+  // the 128 x 128 tile on ranks of more than 8192 rows without a reservation, the 128 x 64 tile elsewhere
+  gemm_tile = (cus == 0 && max_nblk * m > 8192) ? 128 : 64;
+  skip_cols = cus > 0 || gemm_tile == 128;
+  chunk_skip = cus > 0;
+  lat_reg = cus > 0;
+  lat_wide = cus > 0 && p == 1 && npad <= 8192;
+}
+
 Engine::Engine(Device& dev, Comm& comm, int64_t n, int64_t m, const SolveOptions& opt)
     : dev_(dev), comm_(comm), opt_(opt) {
   GJ_REQUIRE(n > 0 && m > 0, "n and m must be positive");
@@ -96,36 +174,27 @@ Engine::Engine(Device& dev, Comm& comm, int64_t n, int64_t m, const SolveOptions
   if (const char* e = std::getenv("GJ_STEP_EVENTS")) step_events_ = std::atoi(e) != 0;
   L_ = Layout::make(n, m, comm.size(), comm.rank());
   GJ_REQUIRE(L_.Nr < (int64_t(1) << 31), "too many block rows");
-  // auto depth: profiles/small_n_sweep.md (N=8192: depth 2 34.6 vs 35.9 ms; N=16384: 4 wins), and
-  // 8 on ranks of <= 4096 rows of a large matrix (p = 8 at N = 32768: K = 1024 halves the panel
-  // boundaries the pivot chain must hide behind a short trailing update; emulated under the
-  // communication-cost model 0.167 vs 0.177 s, while depth 6 / 8 lose at p = 1 / 2 / 4 and at
-  // N = 16384: profiles/depth_pgt1.md)
-  const bool small_rank = L_.p > 1 && L_.max_nblk * L_.m <= 4096;
-  // Depth 2 on p > 1 ranks of <= 2048 rows (p = 8 at N = 16384) is 0.0382 vs 0.0408 s per emulated
-  // rank under the direct 50 GB/s model (profiles/depth_pgt1.md), but it is the configuration of
-  // the round-3 wrong inverse (p = 8, depth 2, async ranks), whose cause is not localised
-  // (profiles/verify_r6.md): p > 1 keeps depth 4 by default; --depth 2 selects it explicitly.
-  // (One GPU at N = 32768, depth 8 with the co-resident candidate inverse: 0.9 % faster on one box,
-  // 0.5-0.8 % slower on another, same-box A/Bs of round 4 -- not adopted, profiles/rocprof_n32768_r4.md.)
-  const int want = opt_.depth > 0 ? opt_.depth
-                   : (L_.p == 1 && L_.npad <= 8192) ? 2
-                   : (small_rank && L_.npad > 16384) ? 8 : 4;
-  d_ = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)want, (int64_t)kMaxDepth, L_.Nr}));
+  // The size-selected choices come from the planner (plan_policy); GJ_POLICY_LIKE=<n>x<p> hands it
+  // another problem's layout for the depth, the reservation and the switches (tests only)
+  int rc = opt_.reserve_cus;
+  if (const char* e = std::getenv("GJ_RESERVE_CUS")) rc = std::atoi(e);
+  PolicyPlan plan = plan_policy(n, m, (int)L_.p, (int)L_.k, opt_.dtype, dev_.on_gpu(), opt_.depth, opt_.chunk_cols, rc);
+  if (const char* e = std::getenv("GJ_POLICY_LIKE")) {
+    char *e1 = nullptr, *e2 = nullptr;
+    const long long ln = std::strtoll(e, &e1, 10);
+    const long long lp = (e1 != e && *e1 == 'x') ? std::strtoll(e1 + 1, &e2, 10) : 0;
+    if (ln <= 0 || lp <= 0 || lp > (1 << 20) || e2 == e1 + 1 || *e2 != 0)
+      throw Error(Status::BadArgs, std::string("GJ_POLICY_LIKE: expected <n>x<p>, got \"") + e + "\"");
+    plan = plan_policy(ln, m, (int)lp, (int)std::min<int64_t>(L_.k, lp - 1), opt_.dtype, dev_.on_gpu(), opt_.depth,
+                       opt_.chunk_cols, rc);
+  }
+  d_ = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)plan.depth, L_.Nr));
   f_ = d_;
   if (const char* e = std::getenv("GJ_FIRST_DEPTH"))
     if (std::atoi(e) > 0) f_ = (int)std::min<int64_t>({(int64_t)std::atoi(e), (int64_t)d_, L_.Nr});
 
-  // Column chunk plan: fixed partition of the Nr block columns into runs of a multiple of d blocks.
-  int64_t target_cols = opt_.chunk_cols;
-  // 8192 columns: measured 2-4 % faster than 4096 / 16384 in the p = 2, 4, 8 critical-path
-  // emulation at N = 32768 (fewer GEMM tails per panel, still 4 chunks to pipeline the broadcast)
-  if (target_cols <= 0)
-    target_cols = std::max<int64_t>((L_.npad + 7) / 8, std::min<int64_t>(8192, (L_.npad + 1) / 2));
-  int64_t cw = std::max<int64_t>(1, target_cols / m);
-  cw = ((cw + d_ - 1) / d_) * d_;
-  // (chunk boundaries sit on panel boundaries: with a shallower first panel, at f_ + k d_ -- the
-  // first chunk f_ blocks wider)
+  // Column chunk plan: fixed partition of the Nr block columns into runs of a multiple of d blocks
+  // (plan_chunks, from this engine's own layout and depth; GJ_CHUNK_PLAN names one)
   if (const char* e = std::getenv("GJ_CHUNK_PLAN")) {
     // explicit plan for A/B runs: comma-separated block counts, each a multiple of d, summing to Nr
     int64_t b = 0;
@@ -142,42 +211,25 @@ Engine::Engine(Device& dev, Comm& comm, int64_t n, int64_t m, const SolveOptions
     }
     GJ_REQUIRE(b == L_.Nr, "GJ_CHUNK_PLAN: block counts must sum to the number of block columns");
   } else {
-    for (int64_t b = 0; b < L_.Nr;) {
-      const int64_t e = std::min(L_.Nr, b == 0 ? cw + (f_ < d_ ? f_ : 0) : b + cw);
-      cb0_.push_back(b);
-      cb1_.push_back(e);
-      b = e;
-    }
+    plan_chunks(L_.Nr, L_.npad, m, d_, f_, opt_.chunk_cols, cb0_, cb1_);
   }
   chunk_of_.resize(L_.Nr);
   for (size_t c = 0; c < cb0_.size(); ++c)
     for (int64_t b = cb0_[c]; b < cb1_[c]; ++b) chunk_of_[b] = (int64_t)c;
 
-  // CU reservation for the latency-bound panel factorisation (GJ_RESERVE_CUS overrides).
-  int rc = opt_.reserve_cus;
-  if (const char* e = std::getenv("GJ_RESERVE_CUS")) rc = std::atoi(e);
-  // auto: up to N = 16384 the pivot chain is the critical path and its block inverses only start
-  // on a CU no trailing-update workgroup occupies, so keep 32 CUs (1/8 of the chip) off the MAIN
-  // stream -- the first 32 mask bits, i.e. one CU of every shader engine (bits interleave XCCs, then
-  // SEs: bench/cu_mask_probe.hip), since a launch's workgroups are split evenly over the 32 SEs and
-  // an unbalanced mask makes the smallest SE the straggler (profiles/cu_reserve_sweep.md):
-  // N=8192 p=1 -12 %, emulated p=2/4/8 at N=16384 -10/-16/-14 %.  At N=32768 the GEMM is the
-  // critical path and the mask costs 4-10 % (profiles/cu_reserve_sweep.md) -- except on ranks
-  // with <= 4096 rows (p = 8 at N = 32768), where the pivot chain and the RCCL workgroups of its
-  // collectives need the free CUs: under the communication-cost model p = 8 is 6.6 % faster with
-  // the reservation at 100 GB/s, p = 2 / 4 are 9 / 6 % slower (profiles/cu_reserve_pgt1.md).
-  if (rc < 0) rc = (dev_.on_gpu() && (L_.npad <= 16384 || small_rank)) ? 32 : 0;
-  reserved_cus_ = dev_.reserve_cus(rc);
+  // CU reservation for the latency-bound panel factorisation (GJ_RESERVE_CUS overrides, above)
+  reserved_cus_ = dev_.reserve_cus(plan.reserve_request);
+  plan.grant(reserved_cus_);
   // (round 5, peeled loop: at N <= 8192 on one GPU the 3-stage 4-per-CU build is faster even under
   // the reservation, 25.06 vs 25.43 ms; N = 16384 keeps 5 per CU, 153.9 vs 156.1 ms,
   // profiles/gemm_peel_r5.md)
-  dense_gemm_ = reserved_cus_ > 0 && !(L_.p == 1 && L_.npad <= 8192);
+  dense_gemm_ = plan.dense_gemm;
   // The 128 x 128 trailing-update tile (3 per CU) on ranks of more than 8192 rows without a CU
   // reservation, where the GEMM is the critical path (N = 32768: 1120 -> 1083.5 ms on one box;
   // emulated p = 2: even); the 128 x 64 tile (4 per CU) elsewhere: under a reservation (N = 8192:
   // 22.7 vs 23.5 ms) and on the 8192-row ranks of p = 4 at N = 32768 (emulated 0.2735 vs 0.2911 s
   // comm-free), whose pivot chain needs the slots (profiles/gemm_tile128_r6.md)
-  gemm_tile_ = (reserved_cus_ == 0 && L_.max_nblk * L_.m > 8192) ? 128 : 64;
+  gemm_tile_ = plan.gemm_tile;
   dev_.set_gemm_tile_hint(gemm_tile_);
   if (const char* e = std::getenv("GJ_DENSE_GEMM")) dense_gemm_ = std::atoi(e) != 0;
   // (Rounds 2-5) candidate inverses on ranks whose trailing update holds every CU (p > 1 without a
@@ -298,19 +350,19 @@ Engine::Engine(Device& dev, Comm& comm, int64_t n, int64_t m, const SolveOptions
   main_cnt_ = 3;
   if (const char* e = std::getenv("GJ_MAIN_CNT")) main_cnt_ = std::atoi(e) & 3;
   if (const char* e = std::getenv("GJ_MAIN_SPLIT")) main_split_ = std::atoi(e);
-  skip_cols_ = reserved_cus_ > 0 || gemm_tile_ == 128;
+  skip_cols_ = plan.skip_cols;
   if (const char* e = std::getenv("GJ_SKIP_COLS")) skip_cols_ = std::atoi(e) != 0;
-  chunk_skip_ = reserved_cus_ > 0;
+  chunk_skip_ = plan.chunk_skip;
   // the chain's latency GEMMs on the register-fed small kernel where CUs are reserved for it
   // (scripts/runs/r5_latk.sh): N = 8192 23.42 -> 22.80 ms, emulated p = 8 at N = 32768 -1.5 / -3.7 %
   // (comm-free / direct 50 GB/s), p = 4 at N = 16384 -4 %; N = 16384 even
-  lat_reg_ = reserved_cus_ > 0;
+  lat_reg_ = plan.lat_reg;
   if (const char* e = std::getenv("GJ_LAT_REG")) lat_reg_ = std::atoi(e) != 0;
   if (const char* e = std::getenv("GJ_CHUNK_SKIP")) chunk_skip_ = std::atoi(e) != 0;
   // (N = 16384, once the register-fed latency kernel exists: that kernel is 0.25 % faster for the
   // 16384-row column update, 149.4 -> 149.0 ms; N = 8192 keeps the LDS-DMA kernel, 22.83 vs 22.92 ms;
   // scripts/runs/r5_colupd.sh)
-  lat_wide_ = reserved_cus_ > 0 && L_.p == 1 && L_.npad <= 8192;
+  lat_wide_ = plan.lat_wide;
   if (const char* e = std::getenv("GJ_LAT_GLDS")) lat_wide_ = std::atoi(e) != 0;
   // GJ_CHUNK_BUILD=23|25|33: the LDS-DMA build of the chunk pass's normalisation GEMMs (COMM).
   // Under a CU reservation MAIN fills its 224 CUs, so COMM's workgroups land on the 32 reserved

@@ -89,6 +89,10 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
     return;
   }
   const Layout& L = eng->layout();
+  {
+    std::lock_guard<std::mutex> lk(sh.mu);
+    sh.rep.policy_ranks[(size_t)rank] = eng->policy();
+  }
   if (rank == 0) {
     std::lock_guard<std::mutex> lk(sh.mu);
     sh.rep.device_desc = dev->describe();
@@ -312,6 +316,7 @@ RunReport run_local(const RunConfig& cfg) {
     }
   }
   sh.input = cfg.input;
+  sh.rep.policy_ranks.resize((size_t)cfg.ranks);
   if (cfg.nrhs < 1) {
     sh.rep.status = Status::BadArgs;
     sh.rep.message = "bad arguments";

@@ -98,7 +98,9 @@ class GaussJordan:
         right-hand side then takes the block path as one column.
         ``cond``: the report gains ``cond`` = {"one", "inf"}, the condition numbers
         ||A||_p ||inv(A)||_p of the matrix the inverse belongs to (after the update, if one is given).
-        With ``equilibrate`` the report gains ``equilibrate`` = {applied, row_exp_range, col_exp_range}."""
+        With ``equilibrate`` the report gains ``equilibrate`` = {applied, row_exp_range, col_exp_range}.
+        ``policy_ranks`` of every report: what each rank's engine chose (Engine.policy without the
+        communicator's entries), one dict per rank."""
         cfg = self._cfg(n)
         if det:
             cfg["det"] = True

@@ -174,6 +174,37 @@ def test_strided_c_in_matches_in_place(native):
             assert _same(_call(c, native, tile, general=True)[0], ref), (M, N, K, tile)
 
 
+# (tile, build): the kernel launch_glds names for it.  Build 25 is the dense (5-per-CU) build, which
+# exists on the 64-wide tile only; 32 on the 128-wide one only.
+BUILDS = {(64, 23): "glds64:t64:b23:peel", (64, 33): "glds64:t64:b33:peel", (64, 25): "glds64:t64:b25:peel",
+          (128, 23): "glds64:t128:b23:peel", (128, 33): "glds64:t128:b33:peel", (128, 32): "glds64:t128:b32:peel"}
+
+
+@pytest.mark.parametrize("M,N,K", [(384, 384, 40), (300, 200, 512)])
+def test_builds_agree_bit_for_bit(M, N, K, native):
+    """Every LDS-DMA build of both tile widths on one call with a zero row block and zero columns: the
+    stage count, the register bound and the tile width may not change a bit (each output element is the
+    same ascending-k chain of v_mfma_f64_16x16x4), which is what lets an engine's inverse be compared
+    across the policies that pick these builds (tests/test_gpu_policy_corners.py)."""
+    c = _case(M, N, K, zr=(128,), zh=128, zc=(16, 144))
+    out = {}
+    for (tile, build), name in BUILDS.items():
+        C = c["Cin"].clone()
+        kw = dict(c["kw"], glds_tile=tile, c_nt=3)
+        if build == 25:
+            kw["dense"] = True
+        else:
+            kw["glds_build"] = build
+        ops.gemm(c["At"], c["B"], C, **kw)
+        assert native.last_gemm_kernel() == name, (tile, build, native.last_gemm_kernel())
+        out[(tile, build)] = C
+    first = out[(64, 23)]
+    err = np.abs(first.cpu().numpy() - c["ref"]).max()
+    assert err < 1e-12 * K, err
+    for key, C in out.items():
+        assert _same(C, first), (key, float((C - first).abs().max()))
+
+
 def test_solve_bits_across_tile_width(native, monkeypatch):
     """p = 1, N = 1024, m = 128, depth 4: the inverse with the 128-wide tile forced has the bits of
     the 64-wide one"""
