@@ -48,6 +48,11 @@
 //                        every column (Engine::solve_rhs_block with bounds; one right-hand side takes
 //                        the block path as one column).  stdout keeps its form; --json gains
 //                        "axb_ferr_cols" and "axb_berr_cols"
+//   --precise            with --rhs: extra-precise refinement, the residual accumulated in twice the
+//                        working precision (Engine::solve_rhs_block with precise; one right-hand side
+//                        takes the block path as one column).  stdout keeps its form; --json gains
+//                        "precise": true, "axb_dx_rel_cols" and "axb_err_est_cols"; --refine then
+//                        defaults to 10 corrections.  Not with --trans (usage, exit 1)
 //   --cond               print "cond: <kappa_1> <kappa_inf>" (||A||_p ||inv(A)||_p from the resident
 //                        inverse, Engine::cond; of A + U V^T after an update) after the residual line
 //                        and after the slogdet line when both are given; --json gains
@@ -129,6 +134,21 @@ static void json_report(const RunConfig& cfg, const RunReport& rep) {
       };
       arr("axb_ferr_cols", [](const RhsResult& c) { return c.ferr; });
       arr("axb_berr_cols", [](const RhsResult& c) { return c.berr; });
+    }
+    if (rep.precise) {  // --precise: one entry per column, at any nrhs (null for a value JSON cannot hold)
+      auto arr = [&](const char* name, auto&& item) {
+        rhs += std::string(", \"") + name + "\": [";
+        for (size_t j = 0; j < rep.rhs_cols.size(); ++j) {
+          char b[64];
+          const double v = item(rep.rhs_cols[j]);
+          std::snprintf(b, sizeof b, "%.6e", v);
+          rhs += (j ? ", " : "") + (std::isfinite(v) ? std::string(b) : std::string("null"));
+        }
+        rhs += "]";
+      };
+      rhs += ", \"precise\": true";
+      arr("axb_dx_rel_cols", [](const RhsResult& c) { return c.dx_rel; });
+      arr("axb_err_est_cols", [](const RhsResult& c) { return c.err_est; });
     }
     if (rep.nrhs > 1) {  // --nrhs K: one entry per column
       auto arr = [&](const char* name, auto&& item) {
@@ -263,6 +283,7 @@ int main(int argc, char* argv[]) {
       else if (a == "--nrhs") cfg.nrhs = std::atoi(val("--nrhs"));
       else if (a == "--trans") cfg.trans = true;
       else if (a == "--bounds") cfg.bounds = true;
+      else if (a == "--precise") cfg.precise = true;
       else if (a == "--cond") cfg.cond = true;
       else if (a == "--out-x") x_file = val("--out-x");
       else if (a == "--refine") cfg.refine = std::atoi(val("--refine"));
@@ -292,6 +313,7 @@ int main(int argc, char* argv[]) {
   if (pos.size() < 2 || pos.size() > 3) return usage(argv[0]);
   const long long n = std::atoll(pos[0]), m = std::atoll(pos[1]);
   if (n <= 0 || m <= 0 || cfg.ranks <= 0 || cfg.print_max < 0) return usage(argv[0]);
+  if (cfg.trans && cfg.precise) return usage(argv[0]);
   cfg.n = n;
   cfg.m = m;
   if (pos.size() == 3) cfg.file = pos[2];

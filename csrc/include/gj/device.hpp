@@ -438,6 +438,21 @@ class Device {
   virtual void panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
                          int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign,
                          const int32_t* active, double* colmax, int s) = 0;
+  // The residual in twice the working precision (Engine::solve_rhs_block with precise):
+  // Y = round_fp64(C_in - P V), the whole sum, C_in included, carried as an unevaluated (hi, lo) pair
+  // of doubles and rounded once.  Operands, active and colmax as in panel_rhs, with these differences:
+  // P is fp64 (any other dt is Status::BadArgs) and there is no sign.  Dot2 (Ogita, Rump, Oishi): per
+  // term p = a v, e = fma(a, v, -p), (s, sigma) = TwoSum(s, p), lo += e + sigma; C_in enters the pair
+  // exactly; partial sums (the GPU's K lanes and K-slices) are pairs added in a fixed order by
+  // double-double additions.  With S = |C_in| + |P| |V| the result obeys, componentwise,
+  //   |Y - (C_in - P V)| <= u |C_in - P V| + 4 ((n + 2) u)^2 S,   u = 2^-53.
+  // Never read: what panel_rhs never reads; the padded local rows of Y are written as C_in (or 0); an
+  // inactive column is neither computed nor written and its colmax is untouched.  A NaN of V reaches Y
+  // also through a zero of P.  No floating-point atomics: two launches on the same inputs give the
+  // same bits.  The executors need not agree to the bit with each other.
+  virtual void panel_rhs_dd(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                            int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy,
+                            const int32_t* active, double* colmax, int s) = 0;
   // dst[g*ldd + j] = src[(q*max_nblk*m + b*m + e)*lds + j] for the global rows g = (b*p + q)*m + e < n
   // and j < k: the rank-major rows Comm::allgather delivers (max_nblk*m rows per rank) into natural
   // row order.  Rows >= n of dst are not written.
@@ -592,6 +607,8 @@ inline int32_t equil_exponent(double amax) {
 // Test probe of Device::panel_rhs, like g_last_gemm_kernel: "host" on the host executor,
 // "rhs<16|32|64>:<f64|f32>:<vec|scalar>:s<split>" on the GPU.
 inline thread_local const char* g_last_rhs_kernel = "";
+// The same of Device::panel_rhs_dd: "host", or "rhsdd<16|32|64>:f64:<vec|scalar>:s<split>".
+inline thread_local const char* g_last_rhs_dd_kernel = "";
 // The same of Device::panel_rhs_t: "host", or "rhst<16|32|64>:<f64|f32>:<vec|scalar>:s<split>".
 inline thread_local const char* g_last_rhs_t_kernel = "";
 // The same of Device::panel_abs_rhs / panel_abs_rhs_t: "host", or

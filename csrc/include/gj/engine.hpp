@@ -157,6 +157,17 @@ struct RhsResult {
   // For trans the same with A^T and inv(A)^T.
   double ferr = std::numeric_limits<double>::quiet_NaN();
   double berr = std::numeric_limits<double>::quiet_NaN();
+  // Extra-precise refinement (solve_rhs_block with precise; NaN when not asked for), LAPACK's xGERFSX
+  // quantities.  With delta_i = ||inv(A) r_i||_inf the size of the correction iterate i would get and
+  // xi_i = ||x_i||_inf:
+  //   dx_rel    delta / xi of the returned iterate (delta alone when xi == 0): the estimate of its
+  //             relative error that the stopping rule looked at
+  //   dx_ratio  the largest delta_i / delta_{i-1} seen (0 if none): the contraction of the iteration
+  //   err_est   max(max(10, sqrt(n)) 2^-53, dx_rel / (1 - dx_ratio)), inf when dx_ratio >= 1 (LAPACK's
+  //             ERR_BNDS_NORM(., LA_LINRX_ERR_I)): the normwise forward error estimate
+  double dx_rel = std::numeric_limits<double>::quiet_NaN();
+  double dx_ratio = std::numeric_limits<double>::quiet_NaN();
+  double err_est = std::numeric_limits<double>::quiet_NaN();
 };
 
 // Result of Engine::cond: the 1- and inf-norms of A (from the rows the caller gives, in fp64) and of
@@ -345,14 +356,32 @@ class Engine : private EnginePanels, private EngineWork {
   // Device::bound_terms with nz_eps = (n + 1) 2^-53, safe1 = (n + 1) DBL_MIN, safe2 = safe1 / 2^-53;
   // r = b - A x is the loop's own residual where it belongs to the returned iterate, else recomputed.
   // About one more sweep per group; x and the rest of the report do not depend on it.
+  // precise: extra-precise refinement (LAPACK 3.2 xGERFSX; Demmel, Hida, Kahan, Li, Mukherjee, Riedy
+  // 2006).  The residual r_i = b - A x_i is accumulated in twice the working precision
+  // (Device::panel_rhs_dd over the fp64 rows, rounded once), the correction d_i = inv(A) r_i is formed
+  // in the engine dtype into a buffer of its own, and each column follows the rule of its size
+  // delta_i = ||d_i||_inf against xi_i = ||x_i||_inf (ColumnRule::step_precise): converged at delta_i <=
+  // 2^-53 xi_i (d_i is not applied); stopped after max_refine corrections, at delta_i > delta_{i-1} / 2
+  // or at a NaN delta, and then the iterate with the smallest delta is returned; otherwise x_{i+1} = x_i
+  // + d_i in fp64.  `tol` is not used in this mode; residual, backward_error and history keep their
+  // definitions, from the doubled residual.  The forward error falls to about u as long as
+  // kappa(A) u < 1, where the fp64 residual leaves kappa(A) u; RhsResult gains dx_rel, dx_ratio and
+  // err_est.  Each rank holds whole rows of A, so the doubled residual needs no sum over the ranks.
+  // One more streaming pass over the inverse per group than without it (the last correction is formed
+  // and not applied).  With bounds the residual of the returned iterate is the doubled one and nz_eps
+  // = 4 ((n + 2) 2^-53)^2, Dot2's rounding term; ferr stays valid but pessimistic there (|inv(A)| |r|
+  // cannot see the cancellation inv(A) r does): err_est is the sharp figure.  trans with precise is
+  // Status::BadArgs: the transposed residual is a sum over the ranks and would need a doubled
+  // all-reduce.  Off (default): allocation, launches and results are exactly those without it.
   RhsBlockResult solve_rhs_block(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                  const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
-                                 int64_t ld, int max_refine, double tol, bool trans = false, bool bounds = false);
+                                 int64_t ld, int max_refine, double tol, bool trans = false, bool bounds = false,
+                                 bool precise = false);
   // The same with B and X in device memory (fp64), e.g. torch CUDA tensors.
   RhsBlockResult solve_rhs_block_device(const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx, int64_t k,
                                         const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
                                         int64_t ld, int max_refine, double tol, bool trans = false,
-                                        bool bounds = false);
+                                        bool bounds = false, bool precise = false);
   // The norms behind the condition numbers kappa_1 and kappa_inf of the matrix the result panel
   // inverts (after solve(); collective).  A as in solve_rhs_block (gen / host_rows / dev_rows_f64,
   // staged once in fp64); Device::row_abs_max and col_abs_sum over A's rows and over the result panel,
@@ -498,12 +527,12 @@ class Engine : private EnginePanels, private EngineWork {
   // rule are its own; what A X = B and A^T X = B differ in (the products, the buffers of the iterate,
   // how the column norms become global, ||A||_inf or ||A||_1) comes from a BlockPath.
   struct BlockPath;
-  void block_path_plain(BlockPath& f, const double* Aw, int64_t kw);
+  void block_path_plain(BlockPath& f, const double* Aw, int64_t kw, bool precise);
   void block_path_trans(BlockPath& f, const double* Aw, int64_t kw);
   RhsBlockResult solve_rhs_block_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                       bool on_device, const GenSpec* gen, const double* host_rows,
                                       const void* dev_rows, int64_t ld, int max_refine, double tol, bool trans,
-                                      bool bounds);
+                                      bool bounds, bool precise);
   // This rank's rows of A in fp64 (ld npad) from the generator, an fp64 device array or host rows;
   // enqueued on MAIN, not waited for.
   void stage_rows_f64(double* Aw, const GenSpec* gen, const double* host_rows, const void* dev_rows, int64_t ld);

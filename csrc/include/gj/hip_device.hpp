@@ -107,6 +107,9 @@ class HipDevice : public Device {
   void panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
                  const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign, const int32_t* active,
                  double* colmax, int s) override;
+  void panel_rhs_dd(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+                    const double* C_in, int64_t ldc, double* Y, int64_t ldy, const int32_t* active, double* colmax,
+                    int s) override;
   void gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L, int64_t k,
                            int s) override;
   void copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows, int64_t k,
@@ -143,7 +146,7 @@ class HipDevice : public Device {
   int bi_hint_ = -1;  // set_block_inverse_hint
   int tile_hint_ = 0;  // set_gemm_tile_hint
   std::vector<void*> events_;
-  // 2, 3: panel_rhs / panel_rhs_t slice partials; 4: slogdet_batch's fp64 images (m > 128)
+  // 2, 3: panel_rhs (panel_rhs_dd: its (hi, lo) pairs) / panel_rhs_t slice partials; 4: slogdet_batch's fp64 images (m > 128)
   void* scratch_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t scratch_sz_[5] = {0, 0, 0, 0, 0};
 };

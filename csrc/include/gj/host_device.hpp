@@ -84,6 +84,9 @@ class HostDevice : public Device {
   void panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
                  const double* C_in, int64_t ldc, double* Y, int64_t ldy, double sign, const int32_t* active,
                  double* colmax, int s) override;
+  void panel_rhs_dd(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+                    const double* C_in, int64_t ldc, double* Y, int64_t ldy, const int32_t* active, double* colmax,
+                    int s) override;
   void gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L, int64_t k,
                            int s) override;
   void copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, int64_t rows, int64_t k,

@@ -44,6 +44,10 @@ struct RunConfig {
   // With rhs / rhs_input: the error bounds of every column (Engine::solve_rhs_block with bounds, the
   // block path at any nrhs >= 1), RhsResult::ferr / berr of RunReport::rhs_cols
   bool bounds = false;
+  // With rhs / rhs_input: extra-precise refinement of every column (Engine::solve_rhs_block with
+  // precise, the block path at any nrhs >= 1), RhsResult::dx_rel / dx_ratio / err_est of
+  // RunReport::rhs_cols.  Not with trans (Status::BadArgs).
+  bool precise = false;
   // ||A||_p ||inv(A)||_p for p = 1 and inf (Engine::cond) of the matrix the inverse belongs to, after
   // the update if one is given
   bool cond = false;
@@ -94,6 +98,7 @@ struct RunReport {
   int nrhs = 1;
   bool trans = false;               // the right-hand sides were solved against A^T
   bool bounds = false;              // rhs_cols carry ferr / berr
+  bool precise = false;             // rhs_cols carry dx_rel / dx_ratio / err_est
   bool cond_computed = false;       // RunConfig::cond: rank 0's norms
   CondResult cond;
   std::vector<RhsResult> rhs_cols;

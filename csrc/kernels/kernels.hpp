@@ -143,6 +143,16 @@ void copy_cols_masked(double* dst, int64_t ldd, const double* src, int64_t lds, 
 void set_rhs_splitk(int s);
 const char* last_rhs_kernel();
 
+// panel_rhs_dd.hip: Device::panel_rhs_dd, Y = round(C_in - P V) from a double-double sum (Dot2), P
+// fp64.  The K-split is panel_rhs's plan and takes its test hook (set_rhs_splitk); scratch: the
+// (hi, lo) partials of the slices, panel_rhs_dd_scratch_bytes(L, k) bytes.  Test probe: the name of
+// this thread's last launch, "rhsdd<16|32|64>:f64:<vec|scalar>:s<split>" ("host" on the host executors).
+size_t panel_rhs_dd_scratch_bytes(const Layout& L, int64_t k);
+void panel_rhs_dd(const double* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv, int64_t k,
+                  const double* C_in, int64_t ldc, double* Y, int64_t ldy, const int32_t* active, double* colmax,
+                  void* scratch, hipStream_t s);
+const char* last_rhs_dd_kernel();
+
 // panel_rhs_t.hip: Device::panel_rhs_t / axpy_cols_masked / col_abs_sum.  scratch: the row-slice
 // partials, panel_rhs_t_scratch_bytes(...) bytes (for the split and load width the launch will use).
 size_t panel_rhs_t_scratch_bytes(DType dt, const void* P, int64_t ldp, const Layout& L, int64_t k);

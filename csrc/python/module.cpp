@@ -176,8 +176,9 @@ py::array_t<double> to_array(const std::vector<double>& v, int64_t r, int64_t c)
 
 }  // namespace
 
-// bounds: the solve was asked for ferr / berr (the keys are absent otherwise)
-static py::dict rhs_info(const RhsResult& rr, bool bounds = false) {
+// bounds: the solve was asked for ferr / berr (the keys are absent otherwise); precise: likewise for
+// dx_rel / dx_ratio / err_est
+static py::dict rhs_info(const RhsResult& rr, bool bounds = false, bool precise = false) {
   py::dict info;
   info["residual"] = rr.residual;
   info["backward_error"] = rr.backward_error;
@@ -187,6 +188,11 @@ static py::dict rhs_info(const RhsResult& rr, bool bounds = false) {
   if (bounds) {
     info["ferr"] = rr.ferr;
     info["berr"] = rr.berr;
+  }
+  if (precise) {
+    info["dx_rel"] = rr.dx_rel;
+    info["dx_ratio"] = rr.dx_ratio;
+    info["err_est"] = rr.err_est;
   }
   return info;
 }
@@ -219,8 +225,10 @@ static py::dict policy_to_dict(const Engine::Policy& pl) {
 }
 
 // max_refine < 0: the default budget of refinement steps, by the engine dtype
-static int refine_budget(const Engine& eng, int max_refine) {
-  return max_refine >= 0 ? max_refine : eng.options().dtype == DType::F64 ? 2 : 10;
+// (precise: LAPACK's ithresh -- the rule stops a column by its correction long before, and two
+// corrections need not reach 2^-53 from an error of kappa u)
+static int refine_budget(const Engine& eng, int max_refine, bool precise = false) {
+  return max_refine >= 0 ? max_refine : (eng.options().dtype == DType::F64 && !precise) ? 2 : 10;
 }
 
 // Device-side time of a launch: `reps` back-to-back run(i), i < reps, on one stream between two
@@ -324,6 +332,9 @@ PYBIND11_MODULE(_C, mod) {
   mod.def("last_rhs_kernel", [] { return std::string(kern::last_rhs_kernel()); },
           "test probe: 'rhs<16|32|64>:<f64|f32>:<vec|scalar>:s<split>' of this thread's last Device.panel_rhs "
           "('host' on the host executor)");
+  mod.def("last_rhs_dd_kernel", [] { return std::string(kern::last_rhs_dd_kernel()); },
+          "test probe: 'rhsdd<16|32|64>:f64:<vec|scalar>:s<split>' of this thread's last Device.panel_rhs_dd "
+          "('host' on the host executors); the split is that of set_rhs_splitk");
   mod.def("set_rhs_t_split", [](int v) { kern::set_rhs_t_split(v); },
           "test hook: row split of the following Device.panel_rhs_t launches on the GPU (0 = auto, s >= 1 forces s)");
   mod.def("last_rhs_t_kernel", [] { return std::string(kern::last_rhs_t_kernel()); },
@@ -555,6 +566,19 @@ PYBIND11_MODULE(_C, mod) {
              run(0);
              return time_launches(d, S_MAIN, reps, run);
            })
+      // The same timing of panel_rhs_dd (Y = -P V from the double-double sum, P fp64)
+      .def("time_panel_rhs_dd",
+           [lay](Device& d, U P, int64_t ldp, int64_t n, int64_t m, int64_t p, int64_t k, U V, int64_t ldv,
+                 int64_t ncols, U Y, int64_t ldy, U colmax, int reps) {
+             py::gil_scoped_release rel;
+             const Layout L = lay(n, m, p, k);
+             auto run = [&](int) {
+               d.panel_rhs_dd(DType::F64, (const void*)P, ldp, L, (const double*)V, ldv, ncols, nullptr, 0, (double*)Y,
+                              ldy, nullptr, (double*)colmax, S_MAIN);
+             };
+             run(0);
+             return time_launches(d, S_MAIN, reps, run);
+           })
       // The same timing of panel_rhs_t (S = P^T V, every column active) and of the K-major GEMM it is
       // measured against (C = At^T B with At = P: M = n, K = the rows of P).
       .def("time_panel_rhs_t",
@@ -726,6 +750,18 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("dt"), py::arg("P"), py::arg("ldp"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"),
            py::arg("V"), py::arg("ldv"), py::arg("ncols"), py::arg("C_in"), py::arg("ldc"), py::arg("Y"),
            py::arg("ldy"), py::arg("sign"), py::arg("active") = U(0), py::arg("colmax") = U(0))
+      // Y = round(C_in - P V) from a double-double sum, P fp64; 0 = a null pointer
+      .def("panel_rhs_dd",
+           [lay](Device& d, const std::string& dt, U P, int64_t ldp, int64_t n, int64_t m, int64_t p, int64_t k,
+                 U V, int64_t ldv, int64_t ncols, U C_in, int64_t ldc, U Y, int64_t ldy, U active, U colmax) {
+             py::gil_scoped_release rel;
+             d.panel_rhs_dd(parse_dtype(dt), (const void*)P, ldp, lay(n, m, p, k), (const double*)V, ldv, ncols,
+                            (const double*)C_in, ldc, (double*)Y, ldy, (const int32_t*)active, (double*)colmax, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("dt"), py::arg("P"), py::arg("ldp"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"),
+           py::arg("V"), py::arg("ldv"), py::arg("ncols"), py::arg("C_in"), py::arg("ldc"), py::arg("Y"),
+           py::arg("ldy"), py::arg("active") = U(0), py::arg("colmax") = U(0))
       // S = P^T V over this rank's real rows (its term of the transposed product); 0 = a null pointer
       .def("panel_rhs_t",
            [lay](Device& d, const std::string& dt, U P, int64_t ldp, int64_t n, int64_t m, int64_t p, int64_t k,
@@ -1158,9 +1194,10 @@ PYBIND11_MODULE(_C, mod) {
       .def("solve_rhs_block",
            [](PyEngine& e, py::object B, py::object gen, py::object rows, uintptr_t rows_f64, int64_t ld,
               uintptr_t b_dev, int64_t ldb, uintptr_t x_dev, int64_t ldx, int64_t ncols, int max_refine,
-              double tol, bool trans, bool bounds) {
+              double tol, bool trans, bool bounds, bool precise) {
              const int64_t n = e.eng->layout().n;
-             max_refine = refine_budget(*e.eng, max_refine);
+             if (trans && precise) throw std::invalid_argument("precise is not available with trans");
+             max_refine = refine_budget(*e.eng, max_refine, precise);
              GenSpec g;
              const GenSpec* gp = nullptr;
              if (!gen.is_none()) {
@@ -1190,7 +1227,7 @@ PYBIND11_MODULE(_C, mod) {
                br = e.eng->solve_rhs_block_device(reinterpret_cast<const double*>(b_dev), ldb,
                                                   reinterpret_cast<double*>(x_dev), ldx, ncols, gp, hrp,
                                                   reinterpret_cast<const void*>(rows_f64), ldr, max_refine, tol,
-                                                  trans, bounds);
+                                                  trans, bounds, precise);
              } else {
                auto b = B.cast<py::array_t<double, py::array::c_style | py::array::forcecast>>();
                if (b.ndim() != 2 || b.shape(0) != n || b.shape(1) < 1)
@@ -1201,12 +1238,12 @@ PYBIND11_MODULE(_C, mod) {
                  py::gil_scoped_release rel;
                  br = e.eng->solve_rhs_block(b.data(), k, x.mutable_data(), k, k, gp, hrp,
                                              reinterpret_cast<const void*>(rows_f64), ldr, max_refine, tol, trans,
-                                             bounds);
+                                             bounds, precise);
                }
                xo = x;
              }
              py::list infos;
-             for (const RhsResult& rc : br.col) infos.append(rhs_info(rc, bounds));
+             for (const RhsResult& rc : br.col) infos.append(rhs_info(rc, bounds, precise));
              py::dict meta;
              meta["sweeps"] = br.sweeps;
              meta["seconds"] = br.seconds;
@@ -1215,13 +1252,16 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("B") = py::none(), py::arg("gen") = py::none(), py::arg("rows") = py::none(),
            py::arg("rows_f64") = 0, py::arg("ld") = 0, py::arg("b_dev") = 0, py::arg("ldb") = 0,
            py::arg("x_dev") = 0, py::arg("ldx") = 0, py::arg("ncols") = 0, py::arg("max_refine") = -1,
-           py::arg("tol") = 1e-15, py::arg("trans") = false, py::arg("bounds") = false,
+           py::arg("tol") = 1e-15, py::arg("trans") = false, py::arg("bounds") = false, py::arg("precise") = false,
            "A X = B (trans: A^T X = B) after solve() for a block of right-hand sides (Engine::solve_rhs_block): every "
            "column refined "
            "in fp64 against A given as gen=(kind, seed), rows (this rank's fp64 rows, host) or rows_f64 / ld (an "
            "fp64 device array).  B: an (n, k) host array -> returns (X, infos, meta); or b_dev / x_dev device "
            "pointers (fp64, n x ncols) -> X is written in place and returned as None.  bounds: every info also "
-           "carries 'ferr' and 'berr' of the returned column (RhsResult)")
+           "carries 'ferr' and 'berr' of the returned column (RhsResult).  precise: extra-precise refinement, the "
+           "residual accumulated in twice the working precision and the columns stopped by the size of their "
+           "correction (tol is not used); every info also carries 'dx_rel', 'dx_ratio' and 'err_est'; not with "
+           "trans (ValueError)")
       .def("cond",
            [](PyEngine& e, py::object gen, py::object rows, uintptr_t rows_f64, int64_t ld) {
              const int64_t n = e.eng->layout().n;
@@ -1451,6 +1491,8 @@ PYBIND11_MODULE(_C, mod) {
     if (c.nrhs < 1) throw std::invalid_argument("nrhs must be >= 1");
     if (d.contains("trans")) c.trans = d["trans"].cast<bool>();
     if (d.contains("bounds")) c.bounds = d["bounds"].cast<bool>();
+    if (d.contains("precise")) c.precise = d["precise"].cast<bool>();
+    if (c.trans && c.precise) throw std::invalid_argument("precise is not available with trans");
     if (d.contains("cond")) c.cond = d["cond"].cast<bool>();
     if (d.contains("keep_solution")) c.keep_solution = d["keep_solution"].cast<bool>();
     if (d.contains("comm_timeout_s")) c.solve.comm_timeout_s = d["comm_timeout_s"].cast<double>();
@@ -1551,9 +1593,10 @@ PYBIND11_MODULE(_C, mod) {
       o["x_head"] = r.x_head;
       if (c.keep_solution) o["x"] = to_array(r.x, c.n, r.nrhs);
       if (r.trans) o["trans"] = true;
-      if (r.nrhs > 1 || r.trans || r.bounds) {
+      if (r.precise) o["precise"] = true;
+      if (r.nrhs > 1 || r.trans || r.bounds || r.precise) {
         py::list cols;
-        for (const RhsResult& rc : r.rhs_cols) cols.append(rhs_info(rc, r.bounds));
+        for (const RhsResult& rc : r.rhs_cols) cols.append(rhs_info(rc, r.bounds, r.precise));
         o["axb_columns"] = cols;
       }
     }

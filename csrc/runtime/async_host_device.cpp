@@ -343,6 +343,14 @@ void AsyncHostDevice::panel_rhs(DType dt, const void* P, int64_t ldp, const Layo
   g_last_rhs_kernel = "host";
   enqueue(s, [=] { inner_.panel_rhs(dt, P, ldp, L, V, ldv, k, C_in, ldc, Y, ldy, sign, active, colmax, s); });
 }
+void AsyncHostDevice::panel_rhs_dd(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V,
+                                   int64_t ldv, int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy,
+                                   const int32_t* active, double* colmax, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_rhs_dd: 1 <= k <= 64 columns");
+  GJ_REQUIRE(dt == DType::F64, "panel_rhs_dd: the panel is fp64");
+  g_last_rhs_dd_kernel = "host";
+  enqueue(s, [=] { inner_.panel_rhs_dd(dt, P, ldp, L, V, ldv, k, C_in, ldc, Y, ldy, active, colmax, s); });
+}
 void AsyncHostDevice::gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L,
                                           int64_t k, int s) {
   enqueue(s, [=] { inner_.gather_rows_natural(dst, ldd, src, lds, L, k, s); });

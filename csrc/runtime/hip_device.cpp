@@ -411,6 +411,17 @@ void HipDevice::panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L,
   kern::panel_rhs(dt, P, ldp, L, V, ldv, k, C_in, ldc, Y, ldy, sign, active, colmax, part, hs(streams_[s]));
   check_launch();
 }
+// (hi, lo) partials: the slot of panel_rhs's, twice its size
+void HipDevice::panel_rhs_dd(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                             int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy,
+                             const int32_t* active, double* colmax, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_rhs_dd: 1 <= k <= 64 columns");
+  GJ_REQUIRE(dt == DType::F64, "panel_rhs_dd: the panel is fp64");
+  void* part = scratch(kern::panel_rhs_dd_scratch_bytes(L, k), 2);
+  kern::panel_rhs_dd(static_cast<const double*>(P), ldp, L, V, ldv, k, C_in, ldc, Y, ldy, active, colmax, part,
+                     hs(streams_[s]));
+  check_launch();
+}
 void HipDevice::gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L,
                                     int64_t k, int s) {
   kern::gather_rows_natural(dst, ldd, src, lds, L, k, hs(streams_[s]));

@@ -619,6 +619,50 @@ void HostDevice::panel_rhs(DType dt, const void* P, int64_t ldp, const Layout& L
   }
 }
 
+// Dot2 (Ogita, Rump, Oishi): the pair starts as (C_in, 0), every term -P[r][c] V[c][j] enters by an exact
+// product (fma) and a TwoSum whose errors collect in lo; one rounding at the end.  The error-free
+// transforms need every operation as written: no contraction in this function.
+void HostDevice::panel_rhs_dd(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V, int64_t ldv,
+                              int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy,
+                              const int32_t* active, double* colmax, int) {
+#pragma clang fp contract(off)
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "panel_rhs_dd: 1 <= k <= 64 columns");
+  GJ_REQUIRE(dt == DType::F64, "panel_rhs_dd: the panel is fp64");
+  g_last_rhs_dd_kernel = "host";
+  std::vector<double> rowmax((size_t)std::max<int64_t>(L.rows, 1) * k, 0.0);
+  parallel_for(L.rows, nthreads_, [&](int64_t r) {
+#pragma clang fp contract(off)
+    const bool real = L.global_row(r) < L.n;
+    for (int64_t j = 0; j < k; ++j) {
+      if (active && active[j] == 0) continue;
+      double y = C_in ? C_in[r * ldc + j] : 0.0;
+      if (real) {
+        double s = y, lo = 0.0;
+        for (int64_t c = 0; c < L.n; ++c) {
+          const double a = -tp<double>(P)[r * ldp + c], v = V[c * ldv + j];
+          const double pr = a * v;
+          const double e = std::fma(a, v, -pr);
+          const double t = s + pr;
+          const double z = t - s;
+          const double sigma = (s - (t - z)) + (pr - z);
+          s = t;
+          lo += e + sigma;
+        }
+        y = s + lo;
+        rowmax[(size_t)(r * k + j)] = std::fabs(y);
+      }
+      Y[r * ldy + j] = y;
+    }
+  });
+  if (!colmax) return;
+  for (int64_t j = 0; j < k; ++j) {
+    if (active && active[j] == 0) continue;
+    double mx = 0.0;
+    for (int64_t r = 0; r < L.rows; ++r) mx = max_keep_nan(mx, rowmax[(size_t)(r * k + j)]);
+    colmax[j] = mx;
+  }
+}
+
 void HostDevice::gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L,
                                      int64_t k, int) {
   const int64_t per = L.max_nblk * L.m;

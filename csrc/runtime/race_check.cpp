@@ -757,6 +757,21 @@ void RaceCheckDevice::panel_rhs(DType dt, const void* P, int64_t ldp, const Layo
   check(s, "panel_rhs", a);
   inner_->panel_rhs(dt, P, ldp, L, V, ldv, k, C_in, ldc, Y, ldy, sign, active, colmax, s);
 }
+void RaceCheckDevice::panel_rhs_dd(DType dt, const void* P, int64_t ldp, const Layout& L, const double* V,
+                                   int64_t ldv, int64_t k, const double* C_in, int64_t ldc, double* Y, int64_t ldy,
+                                   const int32_t* active, double* colmax, int s) {
+  std::vector<Acc> a;
+  if (k >= 1 && k <= kMaxRhs && dt == DType::F64) {  // (the inner device refuses anything else before it touches memory)
+    a.push_back(R(rect(P, ldp, L.n, L.rows, 8), "P"));
+    a.push_back(R(rect(V, ldv, k, L.n, 8), "V"));
+    if (C_in) a.push_back(R(rect(C_in, ldc, k, L.rows, 8), "C_in"));
+    if (active) a.push_back(R(span(active, 4 * k), "active"));
+    a.push_back(W(rect(Y, ldy, k, L.rows, 8), "Y"));
+    if (colmax) a.push_back(W(span(colmax, 8 * k), "colmax"));
+  }
+  check(s, "panel_rhs_dd", a);
+  inner_->panel_rhs_dd(dt, P, ldp, L, V, ldv, k, C_in, ldc, Y, ldy, active, colmax, s);
+}
 void RaceCheckDevice::gather_rows_natural(double* dst, int64_t ldd, const double* src, int64_t lds, const Layout& L,
                                           int64_t k, int s) {
   // rank q's real rows lie within its first nblk(q) * m rows; declared as the whole delivered rows

@@ -87,6 +87,58 @@ struct ColumnRule {
     }
     return save;
   }
+
+  // The rule of extra-precise refinement (solve_rhs_block with precise; LAPACK's xGERFSX): it looks at
+  // the correction, not at the residual.  Iterate `it` has ||b - A x|| = rn (from the doubled
+  // residual), ||x|| = xn and ||inv(A) (b - A x)|| = dn, the size of the correction it would get and
+  // the estimate of its error.  Converged at dn <= 2^-53 xn: the correction is not applied.  Stopped
+  // when the budget is spent, when dn did not halve (LAPACK's rthresh) or when dn is NaN; then the
+  // iterate with the smallest dn is the one returned (a NaN dn: the current one).  Otherwise the column
+  // stays active and the caller adds the correction.  At the stop the report gets dx_ratio and err_est.
+  // Returns whether to keep a copy of this iterate, as step does.
+  double best_dn = std::numeric_limits<double>::infinity(), prev_dn = 0, max_ratio = 0;
+  bool step_precise(RhsResult& r, int it, double rn, double xn, double dn, double an, double bn, int max_refine,
+                    int64_t n) {
+    r.history.push_back(rn / bn);
+    r.residual = rn;
+    r.backward_error = rn / (an * xn + bn);
+    r.dx_rel = xn == 0 ? dn : dn / xn;
+    ret_xn = xn;
+    if (it > 0) max_ratio = max_keep_nan(max_ratio, dn / prev_dn);
+    bool save = false;
+    if (dn < best_dn) {
+      best_dn = dn;
+      best = r;
+      best_xn = xn;
+      save = true;
+    }
+    const bool nan = dn != dn;
+    if (dn <= 0x1p-53 * xn) {
+      r.converged = true;
+      save = true;
+      active = false;
+    } else if (nan || it >= max_refine || (it > 0 && dn > 0.5 * prev_dn)) {
+      if (!nan && dn > best_dn) {  // the best iterate (already saved), with its own report (history kept)
+        best.history = r.history;
+        r = best;
+        ret_xn = best_xn;
+        stale_r = true;
+      } else {
+        save = true;
+      }
+      active = false;
+    } else {
+      prev_dn = dn;
+      r.steps = it + 1;
+    }
+    if (!active) {
+      r.dx_ratio = max_ratio;
+      const double floor_ = std::max(10.0, std::sqrt((double)n)) * 0x1p-53;
+      r.err_est = max_ratio < 1 ? max_keep_nan(floor_, r.dx_rel / (1 - max_ratio))
+                                : std::numeric_limits<double>::infinity();
+    }
+    return save;
+  }
 };
 
 // device / pinned buffers of one call, released together (after the device went idle)
@@ -230,17 +282,18 @@ RhsResult Engine::solve_rhs_impl(const double* b, double* x, const GenSpec* gen,
 // ---------------------------------------------------------------- A X = B, a block of columns
 RhsBlockResult Engine::solve_rhs_block(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                        const GenSpec* gen, const double* host_rows, const void* dev_rows_f64,
-                                       int64_t ld, int max_refine, double tol, bool trans, bool bounds) {
+                                       int64_t ld, int max_refine, double tol, bool trans, bool bounds,
+                                       bool precise) {
   return solve_rhs_block_impl(B, ldb, X, ldx, k, false, gen, host_rows, dev_rows_f64, ld, max_refine, tol, trans,
-                              bounds);
+                              bounds, precise);
 }
 
 RhsBlockResult Engine::solve_rhs_block_device(const double* B_dev, int64_t ldb, double* X_dev, int64_t ldx,
                                               int64_t k, const GenSpec* gen, const double* host_rows,
                                               const void* dev_rows_f64, int64_t ld, int max_refine, double tol,
-                                              bool trans, bool bounds) {
+                                              bool trans, bool bounds, bool precise) {
   return solve_rhs_block_impl(B_dev, ldb, X_dev, ldx, k, true, gen, host_rows, dev_rows_f64, ld, max_refine, tol,
-                              trans, bounds);
+                              trans, bounds, precise);
 }
 
 // What A X = B and A^T X = B differ in, for the block driver.  Vb / Vx / Vr hold B, the iterate and
@@ -260,6 +313,11 @@ struct Engine::BlockPath {
   std::function<void(DType dt, const void* P, const double* V, int64_t kg, const double* C, double* dst,
                      double* nat, double sign, const int32_t* act, double* colmax)>
       product;
+  // precise (A X = B only): r = b - A x from the doubled sum, gathered into Vr, colmax = ||r_j||; the
+  // correction d = inv(A) r in the engine dtype into a buffer of its own, colmax = ||d_j||; x += d,
+  // gathered into Vx, colmax = ||x_j|| -- each for the columns `act`
+  std::function<void(int64_t kg, const int32_t* act, double* colmax)> residual_dd, correction, advance;
+  int norm_sets = 2;  // column-norm vectors (Device::kMaxRhs doubles each) all_ranks makes global
   std::function<const double*(const double* norms)> all_ranks;  // the column norms over all ranks
   std::function<const double*()> result;          // `best` in natural row order
   // The error bounds of a group whose columns have all stopped: xhat = result() (natural order), r
@@ -273,15 +331,17 @@ namespace {
 // xGERFS's constants at order n
 struct BoundConst {
   double nz_eps, safe1, safe2;
-  explicit BoundConst(int64_t n)
-      : nz_eps((double)(n + 1) * 0x1p-53),
+  // precise: the residual comes from Dot2, whose rounding term is gamma^2 (|A| |x| + |b|); the factor 4
+  // covers double-double additions of relative error 2 u^2
+  explicit BoundConst(int64_t n, bool precise = false)
+      : nz_eps(precise ? 4 * ((double)(n + 2) * 0x1p-53) * ((double)(n + 2) * 0x1p-53) : (double)(n + 1) * 0x1p-53),
         safe1((double)(n + 1) * std::numeric_limits<double>::min()),
         safe2(safe1 / 0x1p-53) {}
 };
 }  // namespace
 
 // A X = B: a product is this rank's rows of it (Device::panel_rhs), all-gathered into natural order.
-void Engine::block_path_plain(BlockPath& f, const double* Aw, int64_t kw) {
+void Engine::block_path_plain(BlockPath& f, const double* Aw, int64_t kw, bool precise) {
   BufSet& bufs = f.bufs;
   const int64_t m = L_.m, n = L_.n, p = L_.p;
   const int64_t per = L_.max_nblk * m;  // rows every rank sends to an all-gather
@@ -319,10 +379,26 @@ void Engine::block_path_plain(BlockPath& f, const double* Aw, int64_t kw) {
     dev_.panel_rhs(dt, P, L_.npad, L_, V, kw, kg, C, C ? kw : 0, dst, kw, sign, act, colmax, S_MAIN);
     gather_natural(natural, dst);
   };
+  if (precise) {
+    f.norm_sets = 3;
+    double* d = bufs.get<double>(loc);
+    f.residual_dd = [this, gather_natural, Aw, kw, b = f.b, r = f.r, Vx = f.Vx, Vr = f.Vr](
+                        int64_t kg, const int32_t* act, double* colmax) {
+      dev_.panel_rhs_dd(DType::F64, Aw, L_.npad, L_, Vx, kw, kg, b, kw, r, kw, act, colmax, S_MAIN);
+      gather_natural(Vr, r);
+    };
+    f.correction = [this, kw, d, Vr = f.Vr](int64_t kg, const int32_t* act, double* colmax) {
+      dev_.panel_rhs(opt_.dtype, out_, L_.npad, L_, Vr, kw, kg, nullptr, 0, d, kw, 1.0, act, colmax, S_MAIN);
+    };
+    f.advance = [this, gather_natural, kw, d, x = f.x, Vx = f.Vx](int64_t kg, const int32_t* act, double* colmax) {
+      dev_.axpy_cols_masked(x, kw, x, kw, d, kw, 1.0, real_local_rows(), kg, act, colmax, S_MAIN);
+      gather_natural(Vx, x);
+    };
+  }
   // (a NaN from any rank wins)
-  f.all_ranks = [this, p, mine = std::vector<double>(),
-                 all = std::vector<double>((size_t)(2 * Device::kMaxRhs) * p)](const double* norms) mutable {
-    mine.assign(norms, norms + 2 * Device::kMaxRhs);
+  f.all_ranks = [this, p, sets = (size_t)f.norm_sets, mine = std::vector<double>(),
+                 all = std::vector<double>((size_t)f.norm_sets * Device::kMaxRhs * p)](const double* norms) mutable {
+    mine.assign(norms, norms + sets * Device::kMaxRhs);
     comm_.host_allgather(dev_, mine.data(), all.data(), sizeof(double) * mine.size());
     for (int64_t q = 0; q < p; ++q)
       for (size_t e = 0; e < mine.size(); ++e)
@@ -333,11 +409,14 @@ void Engine::block_path_plain(BlockPath& f, const double* Aw, int64_t kw) {
     gather_natural(Vx, best);
     return (const double*)Vx;
   };
-  f.bounds = [this, gather_natural, Aw, kw, n, b = f.b, D = f.x, r = f.r, Vr = f.Vr](
+  f.bounds = [this, gather_natural, Aw, kw, n, precise, b = f.b, D = f.x, r = f.r, Vr = f.Vr](
                  int64_t kg, const double* xhat, bool redo_r, double* colmax, double* berr) {
-    const BoundConst c(n);
+    const BoundConst c(n, precise);
     dev_.panel_abs_rhs(DType::F64, Aw, L_.npad, L_, xhat, kw, kg, b, kw, D, kw, nullptr, S_MAIN);
-    if (redo_r) dev_.panel_rhs(DType::F64, Aw, L_.npad, L_, xhat, kw, kg, b, kw, r, kw, -1.0, nullptr, nullptr, S_MAIN);
+    if (redo_r && precise)
+      dev_.panel_rhs_dd(DType::F64, Aw, L_.npad, L_, xhat, kw, kg, b, kw, r, kw, nullptr, nullptr, S_MAIN);
+    else if (redo_r)
+      dev_.panel_rhs(DType::F64, Aw, L_.npad, L_, xhat, kw, kg, b, kw, r, kw, -1.0, nullptr, nullptr, S_MAIN);
     // G over r, on the real rows (a prefix of the local rows)
     dev_.bound_terms(r, kw, D, kw, r, kw, real_local_rows(), kg, c.nz_eps, c.safe1, c.safe2, berr, S_MAIN);
     gather_natural(Vr, r);
@@ -401,8 +480,11 @@ void Engine::block_path_trans(BlockPath& f, const double* Aw, int64_t kw) {
 RhsBlockResult Engine::solve_rhs_block_impl(const double* B, int64_t ldb, double* X, int64_t ldx, int64_t k,
                                            bool on_device, const GenSpec* gen, const double* host_rows,
                                            const void* dev_rows, int64_t ld, int max_refine, double tol,
-                                           bool trans, bool bounds) {
+                                           bool trans, bool bounds, bool precise) {
   GJ_REQUIRE(solved_, "solve_rhs_block: solve() first");
+  GJ_REQUIRE(!(trans && precise),
+             "solve_rhs_block: precise is not available with trans (the transposed residual is a sum over the "
+             "ranks and needs a doubled all-reduce)");
   GJ_REQUIRE(k >= 1 && ldb >= k && ldx >= k, "solve_rhs_block: k >= 1 columns, ldb >= k and ldx >= k");
   GJ_REQUIRE(gen || host_rows || dev_rows || real_local_rows() == 0,
              "solve_rhs_block: the matrix (generator or rows) is needed for the fp64 residual");
@@ -420,10 +502,11 @@ RhsBlockResult Engine::solve_rhs_block_impl(const double* B, int64_t ldb, double
   if (trans)
     block_path_trans(f, Aw, kw);
   else
-    block_path_plain(f, Aw, kw);
-  double* dnorm = bufs.get<double>(2 * K);    // ||r_j|| | ||x_j||
+    block_path_plain(f, Aw, kw, precise);
+  const int64_t NS = f.norm_sets;
+  double* dnorm = bufs.get<double>(NS * K);   // ||r_j|| | ||x_j|| (| ||d_j||, precise)
   int32_t* dflag = bufs.get<int32_t>(2 * K);  // active | save-mask
-  double* hnorm = bufs.get_pinned<double>(2 * K);
+  double* hnorm = bufs.get_pinned<double>(NS * K);
   int32_t* hflag = bufs.get_pinned<int32_t>(2 * K);
   std::vector<double> hb;  // a device-resident B's columns on the host, for ||b_j|| only
 
@@ -457,11 +540,15 @@ RhsBlockResult Engine::solve_rhs_block_impl(const double* B, int64_t ldb, double
     std::vector<ColumnRule> rule((size_t)kg);
     RhsResult* rr = out.col.data() + c0;
     for (int it = 0;; ++it) {
-      // r = b - A x in fp64, the whole residual on every rank
-      f.product(DType::F64, Aw, f.Vx, kg, f.b, f.r, f.Vr, -1.0, dflag, dnorm);
-      dev_.copy(hnorm, dnorm, sizeof(double) * 2 * K, S_MAIN);
+      if (precise) {  // r = b - A x from the doubled sum and the correction d = inv(A) r it would get
+        f.residual_dd(kg, dflag, dnorm);
+        f.correction(kg, dflag, dnorm + 2 * K);
+      } else {  // r = b - A x in fp64, the whole residual on every rank
+        f.product(DType::F64, Aw, f.Vx, kg, f.b, f.r, f.Vr, -1.0, dflag, dnorm);
+      }
+      dev_.copy(hnorm, dnorm, sizeof(double) * NS * K, S_MAIN);
       comm_.drain(dev_, S_MAIN);
-      dev_.host_access(hnorm, sizeof(double) * 2 * K, false);
+      dev_.host_access(hnorm, sizeof(double) * NS * K, false);
       const double* norms = f.all_ranks ? f.all_ranks(hnorm) : hnorm;
       out.sweeps = std::max(out.sweeps, it + 1);
       // the per-column decision
@@ -469,7 +556,11 @@ RhsBlockResult Engine::solve_rhs_block_impl(const double* B, int64_t ldb, double
       bool any = false;
       for (int64_t j = 0; j < kg; ++j) {
         ColumnRule& c = rule[(size_t)j];
-        hflag[K + j] = c.active && c.step(rr[j], it, norms[j], norms[K + j], f.an, bn[(size_t)j], max_refine, tol);
+        if (precise)
+          hflag[K + j] = c.active && c.step_precise(rr[j], it, norms[j], norms[K + j], norms[2 * K + j], f.an,
+                                                    bn[(size_t)j], max_refine, n);
+        else
+          hflag[K + j] = c.active && c.step(rr[j], it, norms[j], norms[K + j], f.an, bn[(size_t)j], max_refine, tol);
         hflag[j] = c.active;
         any = any || c.active;
       }
@@ -477,7 +568,10 @@ RhsBlockResult Engine::solve_rhs_block_impl(const double* B, int64_t ldb, double
       dev_.copy_cols_masked(f.best, kw, f.x, kw, f.xrows, kg, dflag + K, S_MAIN);
       if (!any) break;
       // x += inv(A) r for the columns still active (engine dtype, added in fp64)
-      f.product(opt_.dtype, out_, f.Vr, kg, f.x, f.x, f.Vx, 1.0, dflag, dnorm + K);
+      if (precise)
+        f.advance(kg, dflag, dnorm + K);
+      else
+        f.product(opt_.dtype, out_, f.Vr, kg, f.x, f.x, f.Vx, 1.0, dflag, dnorm + K);
     }
     // every column's returned iterate is in `best`
     const double* xhat = f.result();
@@ -486,9 +580,9 @@ RhsBlockResult Engine::solve_rhs_block_impl(const double* B, int64_t ldb, double
       bool redo_r = false;
       for (const ColumnRule& c : rule) redo_r = redo_r || c.stale_r;
       f.bounds(kg, xhat, redo_r, dnorm, dnorm + K);
-      dev_.copy(hnorm, dnorm, sizeof(double) * 2 * K, S_MAIN);
+      dev_.copy(hnorm, dnorm, sizeof(double) * NS * K, S_MAIN);
       comm_.drain(dev_, S_MAIN);
-      dev_.host_access(hnorm, sizeof(double) * 2 * K, false);
+      dev_.host_access(hnorm, sizeof(double) * NS * K, false);
       const double* norms = f.all_ranks ? f.all_ranks(hnorm) : hnorm;
       for (int64_t j = 0; j < kg; ++j) {
         const double xn = rule[(size_t)j].ret_xn;

@@ -225,16 +225,17 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
       res = eng->residual_generated(cfg.gen);
     }
   }
-  if (!sh.b.empty() && (cfg.nrhs > 1 || cfg.trans || cfg.bounds)) {  // trans, bounds: the block path at any width
+  if (!sh.b.empty() && (cfg.nrhs > 1 || cfg.trans || cfg.bounds || cfg.precise)) {  // trans, bounds, precise: the block path at any width
     const int64_t k = cfg.nrhs;
     std::vector<double> x((size_t)cfg.n * k);
     comm->barrier(*dev);
     const auto t0 = std::chrono::steady_clock::now();
-    const int refine = cfg.refine >= 0 ? cfg.refine : (cfg.solve.dtype == DType::F32 ? 10 : 2);
+    // (precise: LAPACK's ithresh; the rule stops a column by its correction long before)
+    const int refine = cfg.refine >= 0 ? cfg.refine : (cfg.solve.dtype == DType::F32 || cfg.precise ? 10 : 2);
     if (src && local.empty()) load();  // the fp64 rows of A (residual_rows keeps them in `local`)
     const RhsBlockResult br = eng->solve_rhs_block(sh.b.data(), k, x.data(), k, k, have_rows ? nullptr : &cfg.gen,
                                                    have_rows ? local.data() : nullptr, nullptr, cfg.n, refine,
-                                                   cfg.refine_tol, cfg.trans, cfg.bounds);
+                                                   cfg.refine_tol, cfg.trans, cfg.bounds, cfg.precise);
     const double tx = comm->host_max(
         *dev, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     if (rank == 0) {
@@ -244,6 +245,7 @@ void rank_main(const RunConfig& cfg, int rank, Shared& sh, std::shared_ptr<Loopb
       r.nrhs = (int)k;
       r.trans = cfg.trans;
       r.bounds = cfg.bounds;
+      r.precise = cfg.precise;
       r.rhs_cols = br.col;
       r.rhs_converged = true;
       size_t worst = 0;

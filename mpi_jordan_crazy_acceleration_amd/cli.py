@@ -23,6 +23,9 @@ given, the residual is against it) and ``--json`` gains ``"equilibrate"``.
 adds ``"axb_ferr_cols"`` / ``"axb_berr_cols"`` to ``--json``.  (One right-hand side without ``--trans``
 or ``--bounds`` runs the one-vector path in ``build/gj`` and the block path here.)  With a file the
 fp64 residual re-reads the rank's rows from it.
+``--precise`` with ``--rhs``: extra-precise refinement, the residual accumulated in twice the working
+precision (``solve_rhs(precise=True)``); stdout keeps its form and ``--json`` gains ``"precise": true``,
+``"axb_dx_rel_cols"`` and ``"axb_err_est_cols"``.  Not with ``--trans`` (usage, exit 1).
 ``--cond``: one more line ``cond: %e %e`` (kappa_1 and kappa_inf, ``DistributedGaussJordan.cond``) after
 the residual line, and after the slogdet line when both are given; ``"cond": {"one", "inf"}`` in
 ``--json``.
@@ -107,6 +110,7 @@ def main(argv=None) -> int:
     ap.add_argument("--nrhs", type=int, default=1)
     ap.add_argument("--trans", action="store_true")
     ap.add_argument("--bounds", action="store_true")
+    ap.add_argument("--precise", action="store_true")
     ap.add_argument("--cond", action="store_true")
     try:
         args, unknown = ap.parse_known_args(argv)
@@ -115,7 +119,7 @@ def main(argv=None) -> int:
     if unknown or not (2 <= len(args.pos) <= 3):
         return _usage(prog)
     n, m = _atoi(args.pos[0]), _atoi(args.pos[1])
-    if n <= 0 or m <= 0 or args.print_max < 0 or args.nrhs < 1:
+    if n <= 0 or m <= 0 or args.print_max < 0 or args.nrhs < 1 or (args.trans and args.precise):
         return _usage(prog)
     path = args.pos[2] if len(args.pos) == 3 else None
     if args.bcast:
@@ -226,7 +230,7 @@ def main(argv=None) -> int:
         infos = None
         if args.rhs:
             x, infos = solver.solve_rhs(_rhs_block(args.rhs, n, args.nrhs, args.seed), A_rows=a_rows, gen=a_gen,
-                                        trans=args.trans, bounds=args.bounds)
+                                        trans=args.trans, bounds=args.bounds, precise=args.precise)
             worst = 0.0
             for c in infos:  # the maximum over the columns, NaN kept
                 worst = c["residual"] if c["residual"] != c["residual"] or c["residual"] > worst else worst
@@ -249,6 +253,10 @@ def main(argv=None) -> int:
                 rec["nrhs"] = args.nrhs
                 if args.bounds:
                     for key in ("ferr", "berr"):
+                        rec[f"axb_{key}_cols"] = [c[key] if c[key] - c[key] == 0 else None for c in infos]
+                if args.precise:
+                    rec["precise"] = True
+                    for key in ("dx_rel", "err_est"):
                         rec[f"axb_{key}_cols"] = [c[key] if c[key] - c[key] == 0 else None for c in infos]
             print(json.dumps(rec), file=sys.stderr, flush=True)
         return 0

@@ -79,7 +79,7 @@ class GaussJordan:
             input: Optional[np.ndarray] = None, keep_inverse: bool = False, repeats: int = 1,
             rhs=None, keep_solution: bool = False, profile: bool = False, nrhs: int = 1,
             trans: bool = False, update=None, det: bool = False, bounds: bool = False,
-            cond: bool = False) -> dict:
+            cond: bool = False, precise: bool = False) -> dict:
         """One CLI-equivalent run.  ``rhs``: None, "ones", "random", a file path, an n-vector or an
         n x k matrix — then x = inv(A) b is computed on the devices, refined in fp64, and
         ``axb_residual`` = ||A x - b||_inf reported.  ``nrhs`` > 1 (implied by a matrix): the block
@@ -96,11 +96,17 @@ class GaussJordan:
         ``bounds`` (with ``rhs``): every entry of ``axb_columns`` gains ``ferr`` and ``berr`` of its
         column (the forward error bound and the componentwise backward error of LAPACK's xGERFS); one
         right-hand side then takes the block path as one column.
+        ``precise`` (with ``rhs``): extra-precise refinement (see :class:`Factored`); every entry of
+        ``axb_columns`` gains ``dx_rel``, ``dx_ratio`` and ``err_est`` and the report holds ``precise`` =
+        True; one right-hand side then takes the block path as one column.  Not with ``trans``
+        (ValueError).
         ``cond``: the report gains ``cond`` = {"one", "inf"}, the condition numbers
         ||A||_p ||inv(A)||_p of the matrix the inverse belongs to (after the update, if one is given).
         With ``equilibrate`` the report gains ``equilibrate`` = {applied, row_exp_range, col_exp_range}.
         ``policy_ranks`` of every report: what each rank's engine chose (Engine.policy without the
         communicator's entries), one dict per rank."""
+        if trans and precise:
+            raise ValueError("precise is not available with trans")
         cfg = self._cfg(n)
         if det:
             cfg["det"] = True
@@ -122,6 +128,8 @@ class GaussJordan:
             cfg["trans"] = True
         if bounds:
             cfg["bounds"] = True
+        if precise:
+            cfg["precise"] = True
         if cond:
             cfg["cond"] = True
         if update is not None:
@@ -189,7 +197,7 @@ class GaussJordan:
         return Factored(self, A)
 
     def solve_resident(self, A: torch.Tensor, b, max_refine: int = -1, tol: float = 1e-15, trans: bool = False,
-                       bounds: bool = False):
+                       bounds: bool = False, precise: bool = False):
         """A x = b for a CUDA tensor A through the engine (Engine::solve_rhs_device): x = inv(A) b by
         the native GEMV, then iterative refinement with the residual b - A x in fp64 against A's
         rows (an fp32 inverse refines to fp64 accuracy on a well-conditioned system, as the CLI's
@@ -197,21 +205,24 @@ class GaussJordan:
         columns together on the device (one pass over each matrix per sweep, B and X never leave the
         GPU).  ``trans``: A^T x = b from the same inverse, always by the block path (a vector is one
         column).  ``bounds``: every info gains ``ferr`` / ``berr`` (see :class:`Factored`), also by the
-        block path.  Returns (x on A's device in A's dtype with b's shape, info per column)."""
+        block path.  ``precise``: extra-precise refinement (see :class:`Factored`), also by the block path;
+        not with ``trans`` (ValueError).  Returns (x on A's device in A's dtype with b's shape, info per column)."""
+        if trans and precise:
+            raise ValueError("precise is not available with trans")
         eng, _ = self._engine_resident(A)
         a64 = A.detach().to(torch.float64).contiguous()
-        return _solve_on_device(eng, a64, A.dtype, b, max_refine, tol, trans, bounds)
+        return _solve_on_device(eng, a64, A.dtype, b, max_refine, tol, trans, bounds, precise)
 
 
 def _solve_on_device(eng, a64: torch.Tensor, out_dtype, b, max_refine: int, tol: float, trans: bool,
-                     bounds: bool = False):
+                     bounds: bool = False, precise: bool = False):
     """solve_resident's solve against an engine that holds inv(A); a64 = A's rows in fp64 on the GPU,
     x is returned there in out_dtype"""
-    if (trans or bounds) and np.ndim(b) == 1:
+    if (trans or bounds or precise) and np.ndim(b) == 1:
         bt = b.detach() if isinstance(b, torch.Tensor) else torch.as_tensor(np.asarray(b, dtype=np.float64))
-        x, infos = _solve_on_device(eng, a64, out_dtype, bt.reshape(-1, 1), max_refine, tol, trans, bounds)
+        x, infos = _solve_on_device(eng, a64, out_dtype, bt.reshape(-1, 1), max_refine, tol, trans, bounds, precise)
         return x.reshape(-1), infos
-    if not (trans or bounds) and (np.ndim(b) != 2 or np.shape(b)[1] == 1):  # one right-hand side: the one-vector path
+    if not (trans or bounds or precise) and (np.ndim(b) != 2 or np.shape(b)[1] == 1):  # one right-hand side: the one-vector path
         torch.cuda.synchronize(a64.device)
         bt = b.detach().to("cpu", torch.float64) if isinstance(b, torch.Tensor) else \
             torch.as_tensor(np.asarray(b, dtype=np.float64))
@@ -227,7 +238,7 @@ def _solve_on_device(eng, a64: torch.Tensor, out_dtype, b, max_refine: int, tol:
     _, infos, _ = eng.solve_rhs_block(rows_f64=a64.data_ptr(), ld=a64.stride(0), b_dev=b64.data_ptr(),
                                       ldb=b64.stride(0), x_dev=x64.data_ptr(), ldx=x64.stride(0),
                                       ncols=b64.shape[1], max_refine=int(max_refine), tol=float(tol),
-                                      trans=bool(trans), bounds=bool(bounds))
+                                      trans=bool(trans), bounds=bool(bounds), precise=bool(precise))
     return x64.to(out_dtype), list(infos)
 
 
@@ -244,6 +255,19 @@ class Factored:
     and fp64 arithmetic whatever the engine dtype; as there, ``ferr`` holds to first order in
     ||I - inv(A) A|| and is to be trusted when the column's ``converged`` is true.  x is the same with
     and without the option (a vector then takes the block path as one column).
+    ``solve(b, precise=True)``: extra-precise refinement (LAPACK 3.2's xGERFSX).  The residual b - A x is
+    accumulated in twice the working precision (Device::panel_rhs_dd: a double-double sum over the kept
+    fp64 rows, rounded once) and every column is stopped by the size of its correction: converged when
+    ||inv(A) r||_inf <= 2^-53 ||x||_inf, stopped when the correction no longer halves or ``max_refine``
+    corrections were applied (10 by default in this mode, LAPACK's ithresh; ``tol`` is not used).  As long as kappa(A) u < 1 for the engine's u the
+    forward error falls to about 2^-53, where the fp64 residual leaves kappa(A) 2^-53: this option
+    changes x.  Every info gains ``dx_rel`` (the last correction's size relative to x), ``dx_ratio``
+    (the worst contraction seen) and ``err_est`` = max(max(10, sqrt(n)) 2^-53, dx_rel / (1 - dx_ratio)),
+    LAPACK's normwise forward error estimate (inf when the corrections did not contract).  With
+    ``bounds`` too, ``ferr`` is computed from the doubled residual and stays a valid but pessimistic
+    bound (|inv(A)| |r| cannot see the cancellation inv(A) r does): ``err_est`` is the sharp figure.  A
+    vector takes the block path as one column; both engine dtypes are accepted (an fp32 engine corrects
+    with its fp32 inverse); not with ``trans`` (ValueError).
     ``cond(p)`` / ``rcond(p)``, p in {1, inf}: ||A||_p ||inv(A)||_p of the handle's matrix from the
     resident inverse, and its reciprocal; cached until the next ``update``.
     A CUDA tensor A stays on its GPU (the resident engine); a numpy
@@ -296,23 +320,27 @@ class Factored:
         + col_exp[j]) the matrix the sweep inverted.  None when the option is off."""
         return self._eng.equil_exponents()
 
-    def solve(self, b, trans: bool = False, max_refine: int = -1, tol: float = 1e-15, bounds: bool = False):
+    def solve(self, b, trans: bool = False, max_refine: int = -1, tol: float = 1e-15, bounds: bool = False,
+              precise: bool = False):
+        if trans and precise:
+            raise ValueError("precise is not available with trans")
         if self._cuda:
             out_dtype = b.dtype if isinstance(b, torch.Tensor) else self._like.dtype
-            x, self.infos = _solve_on_device(self._eng, self._a64, out_dtype, b, max_refine, tol, trans, bounds)
+            x, self.infos = _solve_on_device(self._eng, self._a64, out_dtype, b, max_refine, tol, trans, bounds,
+                                             precise)
             return x
         b_torch = isinstance(b, torch.Tensor)
         bn = b.detach().to("cpu", torch.float64).numpy() if b_torch else np.asarray(b, dtype=np.float64)
         if bn.ndim not in (1, 2) or bn.shape[0] != self.n:
             raise ValueError("b must be an n-vector or an n x k matrix")
-        if not (trans or bounds) and (bn.ndim == 1 or bn.shape[1] == 1):  # the one-vector path, as gj.solve
+        if not (trans or bounds or precise) and (bn.ndim == 1 or bn.shape[1] == 1):  # the one-vector path, as gj.solve
             x, info = self._eng.solve_rhs_rows(np.ascontiguousarray(bn.reshape(-1)), self._a64, int(max_refine),
                                                float(tol))
             self.infos = [info]
         else:
             x, infos, _ = self._eng.solve_rhs_block(np.ascontiguousarray(bn.reshape(self.n, -1)), rows=self._a64,
                                                     max_refine=int(max_refine), tol=float(tol), trans=bool(trans),
-                                                    bounds=bool(bounds))
+                                                    bounds=bool(bounds), precise=bool(precise))
             self.infos = list(infos)
         x = x.reshape(bn.shape)
         return torch.from_numpy(x).to(device=b.device, dtype=b.dtype) if b_torch else x
@@ -467,7 +495,7 @@ def det(A, block_size: int = 128, **kw) -> float:
         return float(sign * np.exp(logabs))
 
 
-def solve(A, b, block_size: int = 128, trans: bool = False, bounds: bool = False, **kw):
+def solve(A, b, block_size: int = 128, trans: bool = False, bounds: bool = False, precise: bool = False, **kw):
     """Solve ``A x = b`` (``trans``: ``A^T x = b``, from the inverse of A itself) via the block
     Gauss-Jordan inverse.
 
@@ -477,17 +505,22 @@ def solve(A, b, block_size: int = 128, trans: bool = False, bounds: bool = False
     over each matrix and gives every column the accuracy of the one-vector call.  A CUDA tensor A
     stays on its GPU (Engine::solve_rhs_device / solve_rhs_block_device); X keeps b's shape.
     ``bounds``: the solve also computes the error bounds of every column (the block path at any width);
-    the return value is x alone -- use :func:`factor` and ``F.infos`` to read them."""
+    the return value is x alone -- use :func:`factor` and ``F.infos`` to read them.
+    ``precise``: extra-precise refinement, the residual accumulated in twice the working precision (see
+    :class:`Factored`): x itself is more accurate, to about 2^-53 as long as kappa(A) u < 1.  Not with
+    ``trans`` (ValueError)."""
+    if trans and precise:
+        raise ValueError("precise is not available with trans")
     is_torch = isinstance(A, torch.Tensor)
     if is_torch and A.is_cuda:
         gj = GaussJordan(block_size=block_size, residual="never", **kw)
-        x, _ = gj.solve_resident(A, b, trans=trans, bounds=bounds)
+        x, _ = gj.solve_resident(A, b, trans=trans, bounds=bounds, precise=precise)
         return x
     bn = b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, dtype=np.float64)
     if bn.ndim in (1, 2):
         a = A.detach().to("cpu", torch.float64).numpy() if is_torch else np.asarray(A, dtype=np.float64)
         gj = GaussJordan(block_size=block_size, residual="never", **kw)
-        rep = gj.run(a.shape[0], input=a, rhs=bn, keep_solution=True, trans=trans, bounds=bounds)
+        rep = gj.run(a.shape[0], input=a, rhs=bn, keep_solution=True, trans=trans, bounds=bounds, precise=precise)
         if rep["status"] == 1:
             raise SingularMatrixError("singular matrix")
         if rep["status"] != 0:

@@ -226,6 +226,31 @@ def panel_rhs(P: torch.Tensor, V: torch.Tensor, Y: torch.Tensor, n: int, m: int,
     return Y
 
 
+def panel_rhs_dd(P: torch.Tensor, V: torch.Tensor, Y: torch.Tensor, n: int, m: int, p: int = 1, k: int = 0,
+                 C_in: torch.Tensor = None, active: torch.Tensor = None, colmax: torch.Tensor = None,
+                 ncols: int = None, device=None) -> torch.Tensor:
+    """Y = round(C_in - P @ V) over the columns c < n (Device::panel_rhs_dd): the residual in twice the
+    working precision.  The whole sum, C_in included, is carried as an unevaluated pair of doubles (Dot2)
+    and rounded once, so |Y - exact| <= u |exact| + 4 ((n + 2) u)^2 (|C_in| + |P| |V|) with u = 2^-53.
+    Operands as in panel_rhs, but ``P`` is fp64 (anything else is an error) and there is no sign.
+    ``device``: the native executor to run on instead of the one of Y's torch device (e.g.
+    ``native.async_host_device()`` for CPU tensors)."""
+    assert V.dtype == Y.dtype == torch.float64 and P.stride(-1) == 1 and V.stride(-1) == 1 and Y.stride(-1) == 1
+    ncols = Y.shape[1] if ncols is None else int(ncols)
+    cp, ldc = 0, 0
+    if C_in is not None:
+        assert C_in.dtype == torch.float64 and C_in.stride(-1) == 1
+        cp, ldc = _p(C_in), C_in.stride(0)
+    if active is not None:
+        assert active.dtype == torch.int32 and active.is_contiguous()
+    if colmax is not None:
+        assert colmax.dtype == torch.float64 and colmax.is_contiguous()
+    (device or device_for(Y)).panel_rhs_dd(_DT[P.dtype], _p(P), P.stride(0), n, m, p, k, _p(V), V.stride(0), ncols,
+                                           cp, ldc, _p(Y), Y.stride(0), 0 if active is None else _p(active),
+                                           0 if colmax is None else _p(colmax))
+    return Y
+
+
 def gather_rows_natural(dst: torch.Tensor, src: torch.Tensor, n: int, m: int, p: int, ncols: int = None) -> torch.Tensor:
     """dst[g] = the row of global index g < n out of ``src``, the rank-major rows an all-gather
     delivers (ceil(Nr / p) * m rows per rank); rows >= n of dst are not written (fp64 views)."""

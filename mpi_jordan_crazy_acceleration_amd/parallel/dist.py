@@ -208,7 +208,7 @@ class DistributedGaussJordan:
         return self.engine.solve()
 
     def solve_rhs(self, B: np.ndarray, A_rows: Optional[np.ndarray] = None, gen=None, max_refine: int = -1,
-                  tol: float = 1e-15, trans: bool = False, bounds: bool = False):
+                  tol: float = 1e-15, trans: bool = False, bounds: bool = False, precise: bool = False):
         """Collective, after solve(): A X = B for the n x k block B (an n-vector counts as k = 1),
         the same full B on every rank, every column refined in fp64 (Engine::solve_rhs_block).  The
         fp64 matrix comes from ``gen`` = (kind, seed) or from ``A_rows``, this rank's rows of A (in
@@ -216,8 +216,14 @@ class DistributedGaussJordan:
         (each rank's term of inv(A)^T B over its own rows, summed over the ranks: no transpose of the
         distributed matrix).  ``bounds``: every info gains ``ferr`` and ``berr``, the forward error bound
         and the componentwise backward error of its column (RhsResult; the same on every rank).
+        ``precise``: extra-precise refinement, the residual accumulated in twice the working precision
+        (each rank holds whole rows of A, so no sum over the ranks is doubled) and every column stopped by
+        the size of its correction; every info gains ``dx_rel``, ``dx_ratio`` and ``err_est`` (RhsResult);
+        ``tol`` is not used; not with ``trans`` (ValueError).
         Returns (X with B's shape, one info dict per column), the same on every
         rank."""
+        if trans and precise:
+            raise ValueError("precise is not available with trans")
         B = np.asarray(B, dtype=np.float64)
         b2 = np.ascontiguousarray(B.reshape(self.n, -1))
         rows = None
@@ -231,7 +237,8 @@ class DistributedGaussJordan:
         else:
             gen = (str(gen[0]), int(gen[1]))
         x, infos, _ = self.engine.solve_rhs_block(b2, gen=gen, rows=rows, max_refine=int(max_refine),
-                                                  tol=float(tol), trans=bool(trans), bounds=bool(bounds))
+                                                  tol=float(tol), trans=bool(trans), bounds=bool(bounds),
+                                                  precise=bool(precise))
         return x.reshape(B.shape), list(infos)
 
     def _rows_or_gen(self, A_rows, gen, what: str):
