@@ -286,7 +286,9 @@ void HostDevice::block_inverse(DType dt, const void* Lt, int64_t ldl, void* inv_
     if (ok)
       for (int64_t i = 0; i < m; ++i) {
         double s = 0.0;
-        for (int64_t j = 0; j < m; ++j) s += std::fabs(W[i * m + j]);
+        // the norm of the inverse as inv_t holds it: fp32 sums the rounded entries, like the GPU
+        for (int64_t j = 0; j < m; ++j)
+          s += std::fabs(dt == DType::F64 ? W[i * m + j] : (double)(float)W[i * m + j]);
         sc = max_keep_nan(sc, s);  // a NaN row sum must reach the test below (std::max drops it)
       }
     // a non-finite score: an entry of the block or of its sweep was NaN or Inf (Device::block_inverse)
