@@ -545,6 +545,30 @@ class Device {
   virtual void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw,
                            bool w_natural, const double* Z, int64_t ldz, int64_t k, double sign, int s) = 0;
 
+  // ---- the gradient matrix of a resident inverse (Engine::grad_matrix, Engine::vjp_inverse) ----
+  // G[i][j] = (accumulate ? G[i][j] : 0) + alpha * (double)P[j][i] + sign * sum_{c<k} W[i][c] * Z[j][c]
+  // for i < n and j < n; 0 <= k <= kMaxRhs, and k > kMaxRhs, k < 0 or n < 0 is Status::BadArgs.
+  //   P     n x n of dtype dt, leading dimension ldp, rows in natural order: the resident result panel
+  //         at p = 1, or a work buffer of the same dtype.  It enters transposed.
+  //   G     fp64, n x n, leading dimension ldg
+  //   W, Z  fp64, n x k in natural row order, leading dimensions ldw, ldz
+  //   sign  +1 or -1; alpha any double
+  // alpha == 0: P is never read and may be null, so a NaN in P does not reach G.  k == 0: W and Z are
+  // never read and may be null.  alpha == 0 && k == 0 && !accumulate writes +0.0.
+  // Both dtypes work in fp64: an fp32 element of P is widened exactly, the k products and their sum
+  // are fp64, the sum is added to alpha * P (one rounding for the product, one for the addition) and
+  // that to G when accumulating (one more); nothing is rounded to dt.
+  // Never read: P's rows and columns >= n, W's and Z's rows >= n and columns >= k, every pitch gap,
+  // and G unless accumulating.  Never written: anything of G outside n x n.  A NaN or an Inf of W or
+  // Z reaches every element it is a term of, also through a zero factor (the rule of gemm and
+  // rank_update).  No atomics and no split of the k sum: two launches on the same inputs give the same
+  // bits.  The executors need not agree to the bit with each other.
+  // GPU: a leading dimension ldg or ldp whose rows one tile cannot address with 32-bit byte offsets is
+  // refused with Status::BadArgs.
+  virtual void grad_matrix(DType dt, const void* P, int64_t ldp, int64_t n, double alpha, const double* W,
+                           int64_t ldw, const double* Z, int64_t ldz, int64_t k, double sign, bool accumulate,
+                           double* G, int64_t ldg, int s) = 0;
+
   // ---- determinants of small blocks (Engine::slogdet over the stashed pivot-block inverses) ----
   // For b < nb: (sign[b], logabs[b]) = slogdet of the m x m block at blocks + b*stride (dtype dt, ld m).
   // Worked in fp64 whatever dt is (an fp32 block is widened exactly).  LU with partial pivoting:
@@ -616,6 +640,9 @@ inline thread_local const char* g_last_rhs_t_kernel = "";
 inline thread_local const char* g_last_abs_kernel = "";
 // The same of Device::rank_update: "host", or "rku<k padded to 4>:<f64|f32>:<vec|scalar>".
 inline thread_local const char* g_last_rank_update_kernel = "";
+// The same of Device::grad_matrix: "host", or "gm<k padded to 4>:<f64|f32|nop>:<vec|scalar>" (nop:
+// alpha == 0, P not read).
+inline thread_local const char* g_last_grad_matrix_kernel = "";
 // The same of Device::slogdet_batch: "host", or "sld:<lds|glob>:<f64|f32>".
 inline thread_local const char* g_last_slogdet_kernel = "";
 // The same of the three equilibration ops: "host", or "eq:<rmax|cmax|scale>:<f64|f32>:<vec|scalar>".

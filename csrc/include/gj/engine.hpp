@@ -403,6 +403,30 @@ class Engine : private EnginePanels, private EngineWork {
   UpdateResult update_inverse(const double* U, int64_t ldu, const double* V, int64_t ldv, int64_t k);
   // The same with U and V in device memory (fp64), e.g. torch CUDA tensors.
   UpdateResult update_inverse_device(const double* U_dev, int64_t ldu, const double* V_dev, int64_t ldv, int64_t k);
+  // The gradient matrix of the resident inverse X = inv(A) (after solve(); solver/grad.cpp):
+  //   G[i][j] = (accumulate ? G[i][j] : 0) + alpha * X[j][i] + sign * sum_{c<k} W[i][c] * Z[j][c],  i, j < n
+  // by one Device::grad_matrix pass over the result panel: with alpha = 0 the gradient -Y X^T of a
+  // solve, with k = 0 and alpha = lbar the gradient lbar inv(A)^T of log|det A|.  G is fp64, n x n
+  // (ldg >= n); W and Z are fp64, n x k in natural row order (ldw, ldz >= k), 0 <= k <=
+  // Device::kMaxRhs (callers apply a wider product in pieces with accumulate); sign is +1 or -1.
+  // The panel is inv(A) of A itself also after update_inverse (then of A + U V^T) and with
+  // SolveOptions::equilibrate.  Single rank: p > 1 is Status::BadArgs (a distributed gradient needs a
+  // distributed transpose).  Nothing is synchronised with the host beyond the final drain.
+  void grad_matrix(double alpha, const double* W, int64_t ldw, const double* Z, int64_t ldz, int64_t k, double sign,
+                   bool accumulate, double* G, int64_t ldg);
+  // The same with W, Z and G in device memory (fp64), e.g. torch CUDA tensors.
+  void grad_matrix_device(double alpha, const double* W_dev, int64_t ldw, const double* Z_dev, int64_t ldz, int64_t k,
+                          double sign, bool accumulate, double* G_dev, int64_t ldg);
+  // The vector-Jacobian product of A -> inv(A) from the resident inverse X: out = -X^T Gbar X^T, for
+  // Gbar and out fp64, n x n (ldg, ldo >= n).  Three steps, no second inversion: M = Gbar^T X by
+  // Device::gemm (GemmOp::Store, Gbar handed over as the K-major A operand), N = X M (Store), out =
+  // -N^T by Device::grad_matrix (alpha = -1, P = N, k = 0).  Gbar is converted to the engine dtype for
+  // the products (Device::upload_convert), so an fp32 engine gives this gradient in fp32 arithmetic.
+  // The two n x npad work buffers live for the call; if they cannot be allocated the call throws
+  // Status::NoBlockMemory.  Single rank: p > 1 is Status::BadArgs.
+  void vjp_inverse(const double* Gbar, int64_t ldg, double* out, int64_t ldo);
+  // The same with Gbar and out in device memory (fp64).
+  void vjp_inverse_device(const double* Gbar_dev, int64_t ldg, double* out_dev, int64_t ldo);
   // sign and log|det| of the matrix whose inverse the result panel holds.  Collective; valid after a
   // successful solve() with SolveOptions::track_det, else Status::BadArgs.  No rows are swapped and the
   // padded system is diag(A, I), so with H_t the stashed inverse of step t's pivot block and sigma the

@@ -261,6 +261,9 @@ class RaceCheckDevice : public Device {
                    int64_t k, double nz_eps, double safe1, double safe2, double* berr, int s) override;
   void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* W, int64_t ldw, bool w_natural,
                    const double* Z, int64_t ldz, int64_t k, double sign, int s) override;
+  void grad_matrix(DType dt, const void* P, int64_t ldp, int64_t n, double alpha, const double* W, int64_t ldw,
+                   const double* Z, int64_t ldz, int64_t k, double sign, bool accumulate, double* G, int64_t ldg,
+                   int s) override;
   void slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb, const int32_t* which,
                      double* sign, double* logabs, int s) override;
   void abs_max_rows(DType dt, const void* X, int64_t ldx, const Layout& L, double* out_nat, int s) override;

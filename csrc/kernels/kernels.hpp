@@ -188,6 +188,14 @@ void rank_update(DType dt, void* X, int64_t ldx, const Layout& L, const double* 
                  const double* Z, int64_t ldz, int64_t k, double sign, hipStream_t s);
 const char* last_rank_update_kernel();
 
+// grad_matrix.hip: Device::grad_matrix, one pass over G with P's tiles transposed through LDS.  Test
+// probe: the name of this thread's last launch, "gm<k padded to 4>:<f64|f32|nop>:<vec|scalar>" ("host" on
+// the host executor).
+void grad_matrix(DType dt, const void* P, int64_t ldp, int64_t n, double alpha, const double* W, int64_t ldw,
+                 const double* Z, int64_t ldz, int64_t k, double sign, bool accumulate, double* G, int64_t ldg,
+                 hipStream_t s);
+const char* last_grad_matrix_kernel();
+
 // slogdet.hip: Device::slogdet_batch.  scratch: slogdet_scratch_bytes(m, nb) bytes (0 for m <= 128, the
 // LDS form).  Test probe: the name of this thread's last launch, "sld:<lds|glob>:<f64|f32>" ("host" on
 // the host executor).

@@ -347,6 +347,9 @@ PYBIND11_MODULE(_C, mod) {
   mod.def("last_rank_update_kernel",[] { return std::string(kern::last_rank_update_kernel()); },
           "test probe: 'rku<k padded to 4>:<f64|f32>:<vec|scalar>' of this thread's last Device.rank_update "
           "('host' on the host executor)");
+  mod.def("last_grad_matrix_kernel", [] { return std::string(kern::last_grad_matrix_kernel()); },
+          "test probe: 'gm<k padded to 4>:<f64|f32|nop>:<vec|scalar>' of this thread's last Device.grad_matrix "
+          "('host' on the host executor)");
   mod.def("last_slogdet_kernel", [] { return std::string(kern::last_slogdet_kernel()); },
           "test probe: 'sld:<lds|glob>:<f64|f32>' of this thread's last Device.slogdet_batch ('host' on the "
           "host executor)");
@@ -819,6 +822,31 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("dt"), py::arg("X"), py::arg("ldx"), py::arg("n"), py::arg("m"), py::arg("p"), py::arg("k"),
            py::arg("W"), py::arg("ldw"), py::arg("w_natural"), py::arg("Z"), py::arg("ldz"), py::arg("ncols"),
            py::arg("sign"))
+      // G (+)= alpha * P^T + sign * W Z^T over n x n, in fp64 (P of dtype dt; 0 = null where never read)
+      .def("grad_matrix",
+           [](Device& d, const std::string& dt, U P, int64_t ldp, int64_t n, double alpha, U W, int64_t ldw, U Z,
+              int64_t ldz, int64_t ncols, double sign, bool accumulate, U G, int64_t ldg) {
+             py::gil_scoped_release rel;
+             d.grad_matrix(parse_dtype(dt), (const void*)P, ldp, n, alpha, (const double*)W, ldw, (const double*)Z,
+                           ldz, ncols, sign, accumulate, (double*)G, ldg, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("dt"), py::arg("P"), py::arg("ldp"), py::arg("n"), py::arg("alpha"), py::arg("W"), py::arg("ldw"),
+           py::arg("Z"), py::arg("ldz"), py::arg("ncols"), py::arg("sign"), py::arg("accumulate"), py::arg("G"),
+           py::arg("ldg"))
+      // The same timing of grad_matrix (the same launch `reps` times: G is only written unless accumulating)
+      .def("time_grad_matrix",
+           [](Device& d, const std::string& dt, U P, int64_t ldp, int64_t n, double alpha, U W, int64_t ldw, U Z,
+              int64_t ldz, int64_t ncols, double sign, bool accumulate, U G, int64_t ldg, int reps) {
+             py::gil_scoped_release rel;
+             const DType t = parse_dtype(dt);
+             auto run = [&](int) {
+               d.grad_matrix(t, (const void*)P, ldp, n, alpha, (const double*)W, ldw, (const double*)Z, ldz, ncols,
+                             sign, accumulate, (double*)G, ldg, S_MAIN);
+             };
+             run(0);
+             return time_launches(d, S_MAIN, reps, run);
+           })
       // (sign, log|det|) of nb blocks of m x m (dtype dt, stride elements apart); which: int32[nb] or 0
       .def("slogdet_batch",
            [](Device& d, const std::string& dt, U blocks, int64_t stride, int64_t m, int64_t nb, U which, U sign,
@@ -1053,6 +1081,50 @@ PYBIND11_MODULE(_C, mod) {
       if (!e.empty()) throw std::runtime_error("loopback_host_max: " + e);
     return got;
   }, py::arg("values"), py::arg("async_") = false);
+  // p virtual ranks on the host (LoopbackComm) invert a well-conditioned n x n matrix, then every rank
+  // calls Engine::grad_matrix and Engine::vjp_inverse: returns each rank's pair of status codes (0 = the
+  // call returned; both are single-rank operations and must refuse p > 1 with BadArgs).
+  mod.def("loopback_grad_probe", [](int p, int64_t n, int64_t m) {
+    if (p < 1 || n < 1) throw std::invalid_argument("loopback_grad_probe: p >= 1, n >= 1");
+    auto hub = std::make_shared<LoopbackHub>(p);
+    std::vector<std::pair<int, int>> got(p, {-1, -1});
+    std::vector<std::string> err(p);
+    {
+      py::gil_scoped_release rel;
+      std::vector<std::thread> th;
+      for (int r = 0; r < p; ++r)
+        th.emplace_back([&, r] {
+          HostDevice dev(1);
+          try {
+            LoopbackComm c(hub, r);
+            Engine eng(dev, c, n, m, SolveOptions());
+            GenSpec g;
+            g.kind = GenKind::RandomShifted;
+            g.seed = 3;
+            eng.generate(g);
+            if (eng.solve().status != Status::Ok) throw std::runtime_error("the inversion failed");
+            std::vector<double> G((size_t)(n * n), 0.0), O((size_t)(n * n), 0.0);
+            auto status_of = [&](auto&& f) {
+              try {
+                f();
+                return (int)Status::Ok;
+              } catch (const Error& e) {
+                return (int)e.status();
+              }
+            };
+            got[r].first = status_of([&] { eng.grad_matrix(1.0, nullptr, 0, nullptr, 0, 0, 1.0, false, G.data(), n); });
+            got[r].second = status_of([&] { eng.vjp_inverse(G.data(), n, O.data(), n); });
+          } catch (const std::exception& e) {
+            err[r] = e.what();
+            hub->fail(err[r]);
+          }
+        });
+      for (auto& t : th) t.join();
+    }
+    for (const auto& e : err)
+      if (!e.empty()) throw std::runtime_error("loopback_grad_probe: " + e);
+    return got;
+  }, py::arg("p"), py::arg("n"), py::arg("m"));
   mod.attr("kHashParts") = (int)Device::kHashParts;
   mod.def("py_comm", [](py::object impl, int rank, int size) {
     return std::shared_ptr<Comm>(new PyComm(std::move(impl), rank, size));
@@ -1336,6 +1408,35 @@ PYBIND11_MODULE(_C, mod) {
            "inv(A) -> inv(A + U V^T) in the result panel (Engine::update_inverse; collective): U, V (n, k) host "
            "arrays, or u_dev / v_dev device pointers (fp64, n x ncols).  status 1 = refused as singular, nothing "
            "written.  Later solve_rhs* / residual_* calls must be given the rows of A + U V^T")
+      .def("grad_matrix",
+           [](PyEngine& e, double alpha, U W, int64_t ldw, U Z, int64_t ldz, int64_t ncols, double sign,
+              bool accumulate, U G, int64_t ldg, bool device) {
+             py::gil_scoped_release rel;
+             if (device)
+               e.eng->grad_matrix_device(alpha, (const double*)W, ldw, (const double*)Z, ldz, ncols, sign, accumulate,
+                                         (double*)G, ldg);
+             else
+               e.eng->grad_matrix(alpha, (const double*)W, ldw, (const double*)Z, ldz, ncols, sign, accumulate,
+                                  (double*)G, ldg);
+           },
+           py::arg("alpha"), py::arg("W") = 0, py::arg("ldw") = 0, py::arg("Z") = 0, py::arg("ldz") = 0,
+           py::arg("ncols") = 0, py::arg("sign") = 1.0, py::arg("accumulate") = false, py::arg("G") = 0,
+           py::arg("ldg") = 0, py::arg("device") = false,
+           "G (+)= alpha * inv(A)^T + sign * W Z^T from the resident inverse (Engine::grad_matrix; one rank): G "
+           "(n x n), W and Z (n x ncols, 0 <= ncols <= 64) are addresses of fp64 arrays with leading dimensions "
+           "ldg, ldw, ldz -- host memory, or device memory with device=True")
+      .def("vjp_inverse",
+           [](PyEngine& e, U Gbar, int64_t ldg, U out, int64_t ldo, bool device) {
+             py::gil_scoped_release rel;
+             if (device)
+               e.eng->vjp_inverse_device((const double*)Gbar, ldg, (double*)out, ldo);
+             else
+               e.eng->vjp_inverse((const double*)Gbar, ldg, (double*)out, ldo);
+           },
+           py::arg("Gbar"), py::arg("ldg"), py::arg("out"), py::arg("ldo"), py::arg("device") = false,
+           "out = -inv(A)^T Gbar inv(A)^T, the vector-Jacobian product of A -> inv(A), from the resident inverse "
+           "(Engine::vjp_inverse; one rank): addresses of fp64 n x n arrays in host memory, or in device memory "
+           "with device=True; the products run in the engine dtype")
       .def("solve_rhs_rows",
            [](PyEngine& e, py::array_t<double, py::array::c_style | py::array::forcecast> b,
               py::array_t<double, py::array::c_style | py::array::forcecast> rows, int max_refine, double tol) {

@@ -400,6 +400,13 @@ void AsyncHostDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& 
   g_last_rank_update_kernel = "host";
   enqueue(s, [=] { inner_.rank_update(dt, X, ldx, L, W, ldw, w_natural, Z, ldz, k, sign, s); });
 }
+void AsyncHostDevice::grad_matrix(DType dt, const void* P, int64_t ldp, int64_t n, double alpha, const double* W,
+                                  int64_t ldw, const double* Z, int64_t ldz, int64_t k, double sign, bool accumulate,
+                                  double* G, int64_t ldg, int s) {
+  GJ_REQUIRE(n >= 0 && k >= 0 && k <= kMaxRhs, "grad_matrix: n >= 0 and 0 <= k <= 64 columns");
+  g_last_grad_matrix_kernel = "host";
+  enqueue(s, [=] { inner_.grad_matrix(dt, P, ldp, n, alpha, W, ldw, Z, ldz, k, sign, accumulate, G, ldg, s); });
+}
 void AsyncHostDevice::slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb,
                                     const int32_t* which, double* sign, double* logabs, int s) {
   GJ_REQUIRE(m >= 1 && nb >= 0 && stride >= m * m, "slogdet_batch: m >= 1, nb >= 0, stride >= m * m");

@@ -481,6 +481,14 @@ void HipDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& L, con
   check_launch();
 }
 
+void HipDevice::grad_matrix(DType dt, const void* P, int64_t ldp, int64_t n, double alpha, const double* W,
+                            int64_t ldw, const double* Z, int64_t ldz, int64_t k, double sign, bool accumulate,
+                            double* G, int64_t ldg, int s) {
+  GJ_REQUIRE(n >= 0 && k >= 0 && k <= kMaxRhs, "grad_matrix: n >= 0 and 0 <= k <= 64 columns");
+  kern::grad_matrix(dt, P, ldp, n, alpha, W, ldw, Z, ldz, k, sign, accumulate, G, ldg, hs(streams_[s]));
+  check_launch();
+}
+
 size_t HipDevice::slogdet_scratch_bytes(int64_t m, int64_t nb) const { return kern::slogdet_scratch_bytes(m, nb); }
 void HipDevice::prepare_slogdet(int64_t m, int64_t nb) {
   const size_t b = kern::slogdet_scratch_bytes(m, nb);

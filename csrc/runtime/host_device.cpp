@@ -818,6 +818,28 @@ void HostDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& L, co
   });
 }
 
+void HostDevice::grad_matrix(DType dt, const void* P, int64_t ldp, int64_t n, double alpha, const double* W,
+                             int64_t ldw, const double* Z, int64_t ldz, int64_t k, double sign, bool accumulate,
+                             double* G, int64_t ldg, int) {
+  GJ_REQUIRE(n >= 0 && k >= 0 && k <= kMaxRhs, "grad_matrix: n >= 0 and 0 <= k <= 64 columns");
+  g_last_grad_matrix_kernel = "host";
+  parallel_for(n, nthreads_, [&](int64_t i) {
+    for (int64_t j = 0; j < n; ++j) {
+      double v = 0.0;  // fp64 for both dtypes, nothing rounded to dt
+      if (k > 0) {
+        double sum = 0.0;
+        for (int64_t c = 0; c < k; ++c) sum += W[i * ldw + c] * Z[j * ldz + c];
+        v = sign * sum;
+      }
+      if (alpha != 0.0) {
+        const double t = alpha * (dt == DType::F64 ? tp<double>(P)[j * ldp + i] : (double)tp<float>(P)[j * ldp + i]);
+        v = k > 0 ? t + v : t;
+      }
+      G[i * ldg + j] = accumulate ? G[i * ldg + j] + v : v;
+    }
+  });
+}
+
 void HostDevice::slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb,
                                const int32_t* which, double* sign, double* logabs, int) {
   GJ_REQUIRE(m >= 1 && nb >= 0 && stride >= m * m, "slogdet_batch: m >= 1, nb >= 0, stride >= m * m");

@@ -889,6 +889,23 @@ void RaceCheckDevice::rank_update(DType dt, void* X, int64_t ldx, const Layout& 
   check(s, "rank_update", a);
   inner_->rank_update(dt, X, ldx, L, Wm, ldw, w_natural, Z, ldz, k, sign, s);
 }
+void RaceCheckDevice::grad_matrix(DType dt, const void* P, int64_t ldp, int64_t n, double alpha, const double* Wm,
+                                  int64_t ldw, const double* Z, int64_t ldz, int64_t k, double sign, bool accumulate,
+                                  double* G, int64_t ldg, int s) {
+  std::vector<Acc> a;
+  if (n > 0 && k >= 0 && k <= kMaxRhs) {  // (the inner device refuses any other k before it touches memory)
+    if (alpha != 0.0) a.push_back(R(rect(P, ldp, n, n, (int64_t)dtype_size(dt)), "P"));  // else never read
+    if (k > 0) {
+      a.push_back(R(rect(Wm, ldw, k, n, 8), "W"));
+      a.push_back(R(rect(Z, ldz, k, n, 8), "Z"));
+    }
+    const auto g = rect(G, ldg, n, n, 8);
+    if (accumulate) a.push_back(R(g, "G"));
+    a.push_back(W(g, "G"));
+  }
+  check(s, "grad_matrix", a);
+  inner_->grad_matrix(dt, P, ldp, n, alpha, Wm, ldw, Z, ldz, k, sign, accumulate, G, ldg, s);
+}
 void RaceCheckDevice::slogdet_batch(DType dt, const void* blocks, int64_t stride, int64_t m, int64_t nb,
                                     const int32_t* which, double* sign, double* logabs, int s) {
   std::vector<Acc> a;

@@ -19,11 +19,13 @@ Python entry points:
 ``cond(A, p)``                         ||A||_p ||inv(A)||_p, p = 1 or inf        -> models.gauss_jordan
 ``run(n, m, ...)``                     the CLI flow in-process (report dict)     -> models.gauss_jordan
 ``DistributedGaussJordan``             one rank per process over torch.distributed -> parallel.dist
+``autograd``                           differentiable factor / solve / slogdet / inverse -> autograd
 ``ops``                                kernel-level wrappers (tests, profiling)
 """
 from ._native import load_native, native_available, native_path  # noqa: F401
 from .models.gauss_jordan import (Factored, GaussJordan, SingularMatrixError, cond, det, factor,  # noqa: F401
                                  inverse, run, slogdet, solve)
 from .parallel.dist import DistributedGaussJordan  # noqa: F401
+from . import autograd  # noqa: F401,E402
 
 __version__ = "0.1.0"

@@ -353,6 +353,29 @@ def rank_update(X: torch.Tensor, W: torch.Tensor, Z: torch.Tensor, n: int, m: in
     return X
 
 
+def grad_matrix(P: torch.Tensor, W: torch.Tensor, Z: torch.Tensor, G: torch.Tensor, n: int, alpha: float = 0.0,
+                sign: float = 1.0, accumulate: bool = False, ncols: int = None, device=None) -> torch.Tensor:
+    """G[i, j] = (G[i, j] if accumulate else 0) + alpha * P[j, i] + sign * sum_c W[i, c] * Z[j, c] for i, j < n
+    (Device::grad_matrix), in fp64 whatever P's dtype is: the gradient matrix of a solve or of a
+    log-determinant from a resident inverse ``P`` (fp64 / fp32, n x n, natural row order), which enters
+    transposed.  ``W`` and ``Z`` fp64, n x ncols in natural order, ``G`` fp64, ``sign`` +1 or -1.  ``alpha``
+    == 0: P is never read and may be None; ``ncols`` == 0: W and Z are never read and may be None.
+    Nothing of G outside n x n is written.  Views with unit column stride; ``ncols`` defaults to Z's width
+    (0 without Z; 0..64, else an error); ``device`` as in panel_abs_rhs."""
+    assert G.dtype == torch.float64 and G.stride(-1) == 1
+    assert P is None or P.stride(-1) == 1
+    assert (W is None) == (Z is None)
+    if Z is not None:
+        assert W.dtype == Z.dtype == torch.float64 and W.stride(-1) == 1 and Z.stride(-1) == 1
+    ncols = (Z.shape[1] if Z is not None else 0) if ncols is None else int(ncols)
+    dt = _DT[P.dtype] if P is not None else "fp64"
+    (device or device_for(G)).grad_matrix(dt, 0 if P is None else _p(P), 0 if P is None else P.stride(0), int(n),
+                                          float(alpha), 0 if W is None else _p(W), 0 if W is None else W.stride(0),
+                                          0 if Z is None else _p(Z), 0 if Z is None else Z.stride(0), ncols,
+                                          float(sign), bool(accumulate), _p(G), G.stride(0))
+    return G
+
+
 def axpy_cols_masked(Y: torch.Tensor, S: torch.Tensor, C_in: torch.Tensor = None, sign: float = 1.0,
                      active: torch.Tensor = None, colmax: torch.Tensor = None, ncols: int = None) -> torch.Tensor:
     """Y[:, j] = C_in[:, j] + sign * S[:, j] for the columns with active[j] != 0 (Device::axpy_cols_masked;
