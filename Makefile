@@ -19,8 +19,8 @@ HIPFLAGS  := $(COMMON) --offload-arch=$(ARCH) -mcode-object-version=5 -munsafe-f
 HOSTFLAGS := $(COMMON) -x c++ -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include
 LDLIBS    := -L$(ROCM)/lib -lrccl -lamdhip64 -lrocprofiler-sdk-roctx -lpthread
 
-KERNELS   := gemm blockinv blockinv_mfma blockinv_big blockinv_huge misc panel_rhs panel_rhs_dd panel_rhs_t panel_abs rank_update grad_matrix slogdet equilibrate
-HOST_SRC  := solver/engine solver/refine solver/grad solver/runner runtime/host_device runtime/hip_device \
+KERNELS   := gemm blockinv blockinv_mfma blockinv_big blockinv_huge misc panel_rhs panel_rhs_dd panel_rhs_t panel_abs rank_update grad_matrix slogdet equilibrate batch
+HOST_SRC  := solver/engine solver/refine solver/grad solver/batch solver/runner runtime/host_device runtime/hip_device \
              runtime/loopback_comm runtime/async_loopback_comm runtime/async_host_device \
              runtime/shadow_comm runtime/rccl_comm runtime/comm runtime/race_check io/matrix_io
 

@@ -617,6 +617,42 @@ class Device {
   // bit.
   virtual void scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat,
                           const int32_t* cexp, int s) = 0;
+
+  // ---- a stack of small matrices (BatchSolver, gj/batch.hpp) ----
+  // The stack's side of block_inverse's calling convention.  Matrix b of a stack is n x n, its rows ld
+  // elements apart and the matrices stride elements apart; the block size of the inverter is m >= n
+  // and the matrix enters it as diag(As_b, I) of order m.
+  //
+  // batch_pack: norm[b] = ||A_b||_inf from fp64 row sums (a NaN row sum gives NaN, as in row_abs_max),
+  // exp[b] = equil_exponent(norm[b]), and the negated K-major panel of the scaled stack,
+  //   Lt[c*ldl + b*m + r] = (dt)(-ldexp(A_b[r][c], exp[b]))  for r, c < n,
+  //   -1 on the diagonal and 0 elsewhere                      for n <= r, c < m,
+  // extract_neg_t's convention: block_inverse's W_b is ldexp(A_b, exp[b]).  A64 is fp64.  The scaling is
+  // exact unless the result leaves dt's range (scale_pow2's rule); NaN, +-Inf and +-0 are kept.
+  // Never read: A's pitch gaps and anything outside n x n of a matrix.  Never written: anything outside
+  // the m x nb*m panel.  Refused (Status::BadArgs): n < 1, m < n, nb < 0, lda < n, ldl < nb * m.
+  virtual void batch_pack(DType dt, const double* A64, int64_t stride_a, int64_t lda, int64_t n, int64_t m,
+                          int64_t nb, void* Lt, int64_t ldl, double* norm, int32_t* exp, int s) = 0;
+  // batch_unpack: X_b[i][j] = (dt)ldexp(inv_t[b*m*m + j*m + i], exp[b]) for i, j < n -- block_inverse's
+  // transposed output as row-major inverses of the unscaled matrices; a block with valid[b] == 0 writes
+  // NaN.  inv_t and X are of dtype dt.  Nothing outside n x n of each X_b is written; of inv_t only the
+  // leading n x n of a valid block is read.
+  virtual void batch_unpack(DType dt, const void* inv_t, int64_t n, int64_t m, int64_t nb, const int32_t* exp,
+                            const int32_t* valid, void* X, int64_t stride_x, int64_t ldx, int s) = 0;
+  // batch_rhs: Y_b = C_in_b + sign * M_b V_b for b < nb: M_b n x n of dtype dt, V_b, C_in_b and Y_b fp64
+  // n x k with 1 <= k <= kMaxRhs (else Status::BadArgs), sign +1 or -1.  Both dtypes work in fp64: an fp32
+  // element of M is widened exactly, V is not rounded, the products and their sum are fp64.
+  //   active  int32[nb*k] (device) or null: column j of matrix b with active[b*k + j] == 0 is neither
+  //           read (C_in, Y) nor written, and its colmax entry is left alone
+  //   colmax  double[nb*k] (device) or null: colmax[b*k + j] = max_r |Y_b[r][j]|, NaN kept
+  //   C_in    null = 0; may be Y itself (then with Y's strides)
+  // Never read: every pitch gap.  A NaN or an Inf of V reaches every element it is a term of, also
+  // through a zero of M.  Each sum has one fixed order and there are no floating-point atomics: two
+  // launches on the same inputs give the same bits.  The executors need not agree to the bit.
+  virtual void batch_rhs(DType dt, const void* M, int64_t stride_m, int64_t ldm, int64_t n, int64_t nb,
+                         const double* V, int64_t stride_v, int64_t ldv, int64_t k, const double* C_in,
+                         int64_t stride_c, int64_t ldc, double* Y, int64_t stride_y, int64_t ldy, double sign,
+                         const int32_t* active, double* colmax, int s) = 0;
 };
 
 // The exponent rule of the equilibration, one place for the engine and every executor's tests: the e
@@ -647,5 +683,8 @@ inline thread_local const char* g_last_grad_matrix_kernel = "";
 inline thread_local const char* g_last_slogdet_kernel = "";
 // The same of the three equilibration ops: "host", or "eq:<rmax|cmax|scale>:<f64|f32>:<vec|scalar>".
 inline thread_local const char* g_last_equil_kernel = "";
+// The same of the three stack ops: "host", or "bpack:<f64|f32>" / "bunpack:<f64|f32>" /
+// "brhs<16|32|64>:<f64|f32>:<vec|scalar>".
+inline thread_local const char* g_last_batch_kernel = "";
 
 }  // namespace gj

@@ -137,6 +137,14 @@ class HipDevice : public Device {
                     int s) override;
   void scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L, const int32_t* rexp_nat, const int32_t* cexp,
                   int s) override;
+  void batch_pack(DType dt, const double* A64, int64_t stride_a, int64_t lda, int64_t n, int64_t m, int64_t nb,
+                  void* Lt, int64_t ldl, double* norm, int32_t* exp, int s) override;
+  void batch_unpack(DType dt, const void* inv_t, int64_t n, int64_t m, int64_t nb, const int32_t* exp,
+                    const int32_t* valid, void* X, int64_t stride_x, int64_t ldx, int s) override;
+  void batch_rhs(DType dt, const void* M, int64_t stride_m, int64_t ldm, int64_t n, int64_t nb, const double* V,
+                 int64_t stride_v, int64_t ldv, int64_t k, const double* C_in, int64_t stride_c, int64_t ldc,
+                 double* Y, int64_t stride_y, int64_t ldy, double sign, const int32_t* active, double* colmax,
+                 int s) override;
   size_t slogdet_scratch_bytes(int64_t m, int64_t nb) const override;
   void prepare_slogdet(int64_t m, int64_t nb) override;
 

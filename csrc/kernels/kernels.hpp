@@ -218,5 +218,17 @@ void set_equil_col_split(int s);
 void set_equil_nt(int on);
 const char* last_equil_kernel();
 
+// batch.hip: Device::batch_pack / batch_unpack / batch_rhs over a stack of small matrices.  Test probe:
+// the name of this thread's last launch of the three, "bpack:<f64|f32>", "bunpack:<f64|f32>" or
+// "brhs<16|32|64>:<f64|f32>:<vec|scalar>" ("host" on the host executors).
+void batch_pack(DType dt, const double* A64, int64_t stride_a, int64_t lda, int64_t n, int64_t m, int64_t nb,
+                void* Lt, int64_t ldl, double* norm, int32_t* exp, hipStream_t s);
+void batch_unpack(DType dt, const void* inv_t, int64_t n, int64_t m, int64_t nb, const int32_t* exp,
+                  const int32_t* valid, void* X, int64_t stride_x, int64_t ldx, hipStream_t s);
+void batch_rhs(DType dt, const void* M, int64_t stride_m, int64_t ldm, int64_t n, int64_t nb, const double* V,
+               int64_t stride_v, int64_t ldv, int64_t k, const double* C_in, int64_t stride_c, int64_t ldc, double* Y,
+               int64_t stride_y, int64_t ldy, double sign, const int32_t* active, double* colmax, hipStream_t s);
+const char* last_batch_kernel();
+
 }  // namespace kern
 }  // namespace gj

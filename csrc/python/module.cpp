@@ -14,6 +14,7 @@
 #include <tuple>
 
 #include "gj/async_host_device.hpp"
+#include "gj/batch.hpp"
 #include "gj/comms.hpp"
 #include "gj/engine.hpp"
 #include "gj/hip_device.hpp"
@@ -356,6 +357,9 @@ PYBIND11_MODULE(_C, mod) {
   mod.def("last_equil_kernel", [] { return std::string(kern::last_equil_kernel()); },
           "test probe: 'eq:<rmax|cmax|scale>:<f64|f32>:<vec|scalar>' of this thread's last Device.abs_max_rows / "
           "abs_max_cols / scale_pow2 ('host' on the host executor)");
+  mod.def("last_batch_kernel", [] { return std::string(kern::last_batch_kernel()); },
+          "test probe: 'bpack:<f64|f32>', 'bunpack:<f64|f32>' or 'brhs<16|32|64>:<f64|f32>:<vec|scalar>' of this "
+          "thread's last Device.batch_pack / batch_unpack / batch_rhs ('host' on the host executors)");
   mod.def("set_equil_col_split", [](int v) { kern::set_equil_col_split(v); },
           "test hook: row split of the following Device.abs_max_cols launches on the GPU (0 = auto, s >= 1 forces s)");
   mod.def("set_equil_nt", [](bool on) { kern::set_equil_nt(on ? 1 : 0); },
@@ -859,6 +863,60 @@ PYBIND11_MODULE(_C, mod) {
            py::arg("dt"), py::arg("blocks"), py::arg("stride"), py::arg("m"), py::arg("nb"), py::arg("which"),
            py::arg("sign"), py::arg("logabs"))
       .def("slogdet_scratch_bytes", [](Device& d, int64_t m, int64_t nb) { return d.slogdet_scratch_bytes(m, nb); })
+      // the stack ops (BatchSolver's): pack / unpack around block_inverse, and the stack's products
+      .def("batch_pack",
+           [](Device& d, const std::string& dt, U A64, int64_t stride_a, int64_t lda, int64_t n, int64_t m, int64_t nb,
+              U Lt, int64_t ldl, U norm, U exp) {
+             py::gil_scoped_release rel;
+             d.batch_pack(parse_dtype(dt), (const double*)A64, stride_a, lda, n, m, nb, (void*)Lt, ldl, (double*)norm,
+                          (int32_t*)exp, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("dt"), py::arg("A64"), py::arg("stride_a"), py::arg("lda"), py::arg("n"), py::arg("m"),
+           py::arg("nb"), py::arg("Lt"), py::arg("ldl"), py::arg("norm"), py::arg("exp"))
+      .def("batch_unpack",
+           [](Device& d, const std::string& dt, U inv_t, int64_t n, int64_t m, int64_t nb, U exp, U valid, U X,
+              int64_t stride_x, int64_t ldx) {
+             py::gil_scoped_release rel;
+             d.batch_unpack(parse_dtype(dt), (const void*)inv_t, n, m, nb, (const int32_t*)exp, (const int32_t*)valid,
+                            (void*)X, stride_x, ldx, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("dt"), py::arg("inv_t"), py::arg("n"), py::arg("m"), py::arg("nb"), py::arg("exp"),
+           py::arg("valid"), py::arg("X"), py::arg("stride_x"), py::arg("ldx"))
+      .def("batch_rhs",
+           [](Device& d, const std::string& dt, U M, int64_t stride_m, int64_t ldm, int64_t n, int64_t nb, U V,
+              int64_t stride_v, int64_t ldv, int64_t ncols, U C_in, int64_t stride_c, int64_t ldc, U Y, int64_t stride_y,
+              int64_t ldy, double sign, U active, U colmax) {
+             py::gil_scoped_release rel;
+             d.batch_rhs(parse_dtype(dt), (const void*)M, stride_m, ldm, n, nb, (const double*)V, stride_v, ldv, ncols,
+                         (const double*)C_in, stride_c, ldc, (double*)Y, stride_y, ldy, sign, (const int32_t*)active,
+                         (double*)colmax, S_MAIN);
+             d.sync_stream(S_MAIN);
+           },
+           py::arg("dt"), py::arg("M"), py::arg("stride_m"), py::arg("ldm"), py::arg("n"), py::arg("nb"), py::arg("V"),
+           py::arg("stride_v"), py::arg("ldv"), py::arg("ncols"), py::arg("C_in"), py::arg("stride_c"),
+           py::arg("ldc"), py::arg("Y"), py::arg("stride_y"), py::arg("ldy"), py::arg("sign"),
+           py::arg("active") = U(0), py::arg("colmax") = U(0))
+      // device time per launch (microseconds) of the stack ops, for bench/bench_batched.py
+      .def("time_batch_op",
+           [](Device& d, const std::string& which, const std::string& dt, U A, U B, U C, U e, U v, int64_t n, int64_t m,
+              int64_t nb, int64_t ncols, int reps) {
+             py::gil_scoped_release rel;
+             const DType t = parse_dtype(dt);
+             auto run = [&](int) {
+               if (which == "pack")  // A: fp64 stack, B: Lt, C: norm
+                 d.batch_pack(t, (const double*)A, n * n, n, n, m, nb, (void*)B, nb * m, (double*)C, (int32_t*)e, S_MAIN);
+               else if (which == "unpack")  // A: inv_t, B: X
+                 d.batch_unpack(t, (const void*)A, n, m, nb, (const int32_t*)e, (const int32_t*)v, (void*)B, n * n, n,
+                                S_MAIN);
+               else  // A: M, B: V, C: Y
+                 d.batch_rhs(t, (const void*)A, n * n, n, n, nb, (const double*)B, n * ncols, ncols, ncols, nullptr, 0, 0,
+                             (double*)C, n * ncols, ncols, 1.0, nullptr, nullptr, S_MAIN);
+             };
+             run(0);
+             return time_launches(d, S_MAIN, reps, run);
+           })
       .def("axpy_cols_masked",
            [](Device& d, U Y, int64_t ldy, U C_in, int64_t ldc, U S, int64_t lds, double sign, int64_t rows,
               int64_t ncols, U active, U colmax) {
@@ -972,6 +1030,99 @@ PYBIND11_MODULE(_C, mod) {
   // the asynchronous host executor (its own worker threads per stream), for per-op tests
   mod.def("async_host_device", [](int nthreads) { return std::shared_ptr<Device>(new AsyncHostDevice(nthreads)); },
           py::arg("nthreads") = 1);
+
+  // A host executor under the schedule checker (gj/race_check.hpp), for drivers that take a Device:
+  // returns (device, checker); async: the asynchronous executor (its own worker threads per stream).
+  py::class_<HbChecker, std::shared_ptr<HbChecker>>(mod, "HbChecker")
+      .def("races", &HbChecker::races)
+      .def("ops", &HbChecker::ops)
+      .def("reports", &HbChecker::reports);
+  mod.def("race_check_host_device",
+          [](bool async, int nthreads) {
+            auto hb = std::make_shared<HbChecker>();
+            std::unique_ptr<Device> inner;
+            if (async) inner.reset(new AsyncHostDevice(nthreads));
+            else inner.reset(new HostDevice(nthreads));
+            std::shared_ptr<Device> dev(new RaceCheckDevice(std::move(inner), hb, "batch"));
+            return py::make_tuple(dev, hb);
+          },
+          py::arg("async") = true, py::arg("nthreads") = 1);
+
+  // A stack of small matrices (gj/batch.hpp).  Pointers are integers: memory of the solver's device
+  // (host memory on the host executors).
+  struct PyBatch {
+    std::shared_ptr<Device> dev;  // outlives the solver
+    std::unique_ptr<BatchSolver> bs;
+    BatchSolveInfo last;
+  };
+  py::class_<PyBatch>(mod, "BatchSolver")
+      .def(py::init([](std::shared_ptr<Device> dev, const std::string& dt, int64_t n, int64_t nb, double eps,
+                       size_t workspace_bytes) {
+             auto p = std::make_unique<PyBatch>();
+             p->dev = dev;
+             p->bs = std::make_unique<BatchSolver>(*dev, parse_dtype(dt), n, nb, eps, workspace_bytes);
+             return p;
+           }),
+           py::arg("device"), py::arg("dtype"), py::arg("n"), py::arg("nb"), py::arg("eps") = 1e-15,
+           py::arg("workspace_bytes") = 0)
+      .def("factor",
+           [](PyBatch& b, U A, int64_t stride_a, int64_t lda) {
+             py::gil_scoped_release rel;
+             b.bs->factor((const double*)A, stride_a, lda);
+           },
+           py::arg("A"), py::arg("stride_a"), py::arg("lda"))
+      .def("inverse",
+           [](PyBatch& b, U X, int64_t stride_x, int64_t ldx) {
+             py::gil_scoped_release rel;
+             b.bs->inverse((void*)X, stride_x, ldx);
+           },
+           py::arg("X"), py::arg("stride_x"), py::arg("ldx"))
+      .def("solve",
+           [](PyBatch& b, U B, int64_t stride_b, int64_t ldb, U X, int64_t ncols, int max_refine,
+              double tol) {
+             BatchSolveInfo r;
+             {
+               py::gil_scoped_release rel;
+               r = b.bs->solve((const double*)B, stride_b, ldb, (double*)X, ncols, max_refine, tol);
+             }
+             const int64_t nb = b.bs->nb();
+             auto arr = [&](const auto& v, auto zero) {
+               using T = decltype(zero);
+               py::array_t<T> a({nb, ncols});
+               std::copy(v.begin(), v.end(), a.mutable_data());
+               return a;
+             };
+             py::dict d;
+             d["converged"] = arr(r.converged, int32_t(0));
+             d["steps"] = arr(r.steps, int32_t(0));
+             d["residual"] = arr(r.residual, 0.0);
+             d["backward_error"] = arr(r.backward_error, 0.0);
+             d["sweeps"] = r.sweeps;
+             return d;
+           },
+           py::arg("B"), py::arg("stride_b"), py::arg("ldb"), py::arg("X"), py::arg("ncols"),
+           py::arg("max_refine") = -1, py::arg("tol") = 1e-15,
+           "A_b X_b = B_b, refined in fp64; X comes back stack-interleaved, X[(r * nb + b) * ncols + j]")
+      .def("slogdet",
+           [](PyBatch& b) {
+             const int64_t nb = b.bs->nb();
+             py::array_t<double> sg(nb), lg(nb);
+             {
+               py::gil_scoped_release rel;
+               b.bs->slogdet(sg.mutable_data(), lg.mutable_data());
+             }
+             return py::make_tuple(sg, lg);
+           })
+      .def_property_readonly("n", [](PyBatch& b) { return b.bs->n(); })
+      .def_property_readonly("nb", [](PyBatch& b) { return b.bs->nb(); })
+      .def_property_readonly("m", [](PyBatch& b) { return b.bs->m(); })
+      .def_property_readonly("chunk", [](PyBatch& b) { return b.bs->chunk(); })
+      .def_property_readonly("valid", [](PyBatch& b) { return py::array_t<int32_t>(b.bs->valid().size(), b.bs->valid().data()); })
+      .def_property_readonly("exponents", [](PyBatch& b) { return py::array_t<int32_t>(b.bs->exponents().size(), b.bs->exponents().data()); })
+      .def_property_readonly("norms", [](PyBatch& b) { return py::array_t<double>(b.bs->norms().size(), b.bs->norms().data()); })
+      .def_property_readonly("inverse_norms", [](PyBatch& b) { return py::array_t<double>(b.bs->inverse_norms().size(), b.bs->inverse_norms().data()); })
+      .def_property_readonly("inverses_ptr", [](PyBatch& b) { return (U)b.bs->inverses_device(); })
+      .def_property_readonly("a64_ptr", [](PyBatch& b) { return (U)b.bs->a64_device(); });
 
   py::class_<Comm,std::shared_ptr<Comm>>(mod, "Comm")
       .def_property_readonly("size", &Comm::size)

@@ -429,4 +429,30 @@ void AsyncHostDevice::scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L
   enqueue(s, [=] { inner_.scale_pow2(dt, X, ldx, L, rexp_nat, cexp, s); });
 }
 
+void AsyncHostDevice::batch_pack(DType dt, const double* A64, int64_t stride_a, int64_t lda, int64_t n, int64_t m,
+                                 int64_t nb, void* Lt, int64_t ldl, double* norm, int32_t* exp, int s) {
+  GJ_REQUIRE(n >= 1 && m >= n && nb >= 0 && lda >= n && ldl >= nb * m,
+             "batch_pack: 1 <= n <= m, nb >= 0, lda >= n, ldl >= nb * m");
+  g_last_batch_kernel = "host";
+  enqueue(s, [=] { inner_.batch_pack(dt, A64, stride_a, lda, n, m, nb, Lt, ldl, norm, exp, s); });
+}
+void AsyncHostDevice::batch_unpack(DType dt, const void* inv_t, int64_t n, int64_t m, int64_t nb, const int32_t* exp,
+                                   const int32_t* valid, void* X, int64_t stride_x, int64_t ldx, int s) {
+  GJ_REQUIRE(n >= 1 && m >= n && nb >= 0 && ldx >= n, "batch_unpack: 1 <= n <= m, nb >= 0, ldx >= n");
+  g_last_batch_kernel = "host";
+  enqueue(s, [=] { inner_.batch_unpack(dt, inv_t, n, m, nb, exp, valid, X, stride_x, ldx, s); });
+}
+void AsyncHostDevice::batch_rhs(DType dt, const void* M, int64_t stride_m, int64_t ldm, int64_t n, int64_t nb,
+                                const double* V, int64_t stride_v, int64_t ldv, int64_t k, const double* C_in,
+                                int64_t stride_c, int64_t ldc, double* Y, int64_t stride_y, int64_t ldy, double sign,
+                                const int32_t* active, double* colmax, int s) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "batch_rhs: 1 <= k <= 64 columns");
+  GJ_REQUIRE(n >= 1 && nb >= 0, "batch_rhs: n >= 1, nb >= 0");
+  g_last_batch_kernel = "host";
+  enqueue(s, [=] {
+    inner_.batch_rhs(dt, M, stride_m, ldm, n, nb, V, stride_v, ldv, k, C_in, stride_c, ldc, Y, stride_y, ldy, sign,
+                     active, colmax, s);
+  });
+}
+
 }  // namespace gj

@@ -945,4 +945,79 @@ void HostDevice::scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L, con
   });
 }
 
+void HostDevice::batch_pack(DType dt, const double* A64, int64_t stride_a, int64_t lda, int64_t n, int64_t m,
+                            int64_t nb, void* Lt, int64_t ldl, double* norm, int32_t* exp, int) {
+  GJ_REQUIRE(n >= 1 && m >= n && nb >= 0 && lda >= n && ldl >= nb * m,
+             "batch_pack: 1 <= n <= m, nb >= 0, lda >= n, ldl >= nb * m");
+  g_last_batch_kernel = "host";
+  parallel_for(nb, nthreads_, [&](int64_t b) {
+    const double* A = A64 + b * stride_a;
+    double mx = 0.0;
+    for (int64_t r = 0; r < n; ++r) {
+      double sum = 0.0;
+      for (int64_t c = 0; c < n; ++c) sum += std::fabs(A[r * lda + c]);
+      mx = max_keep_nan(mx, sum);
+    }
+    const int e = equil_exponent(mx);
+    norm[b] = mx;
+    exp[b] = e;
+    for (int64_t c = 0; c < m; ++c)
+      for (int64_t r = 0; r < m; ++r) {
+        const double v = (r < n && c < n) ? -std::ldexp(A[r * lda + c], e) : (r < n || c < n) ? 0.0 : r == c ? -1.0 : 0.0;
+        if (dt == DType::F64)
+          tp<double>(Lt)[c * ldl + b * m + r] = v;
+        else
+          tp<float>(Lt)[c * ldl + b * m + r] = (float)v;
+      }
+  });
+}
+
+void HostDevice::batch_unpack(DType dt, const void* inv_t, int64_t n, int64_t m, int64_t nb, const int32_t* exp,
+                              const int32_t* valid, void* X, int64_t stride_x, int64_t ldx, int) {
+  GJ_REQUIRE(n >= 1 && m >= n && nb >= 0 && ldx >= n, "batch_unpack: 1 <= n <= m, nb >= 0, ldx >= n");
+  g_last_batch_kernel = "host";
+  parallel_for(nb, nthreads_, [&](int64_t b) {
+    const bool ok = valid[b] != 0;
+    const int e = exp[b];
+    for (int64_t i = 0; i < n; ++i)
+      for (int64_t j = 0; j < n; ++j) {
+        const int64_t src = b * m * m + j * m + i, dst = b * stride_x + i * ldx + j;
+        if (dt == DType::F64)
+          tp<double>(X)[dst] = ok ? std::ldexp(tp<double>(inv_t)[src], e) : std::numeric_limits<double>::quiet_NaN();
+        else
+          tp<float>(X)[dst] =
+              ok ? (float)std::ldexp((double)tp<float>(inv_t)[src], e) : std::numeric_limits<float>::quiet_NaN();
+      }
+  });
+}
+
+void HostDevice::batch_rhs(DType dt, const void* M, int64_t stride_m, int64_t ldm, int64_t n, int64_t nb,
+                           const double* V, int64_t stride_v, int64_t ldv, int64_t k, const double* C_in,
+                           int64_t stride_c, int64_t ldc, double* Y, int64_t stride_y, int64_t ldy, double sign,
+                           const int32_t* active, double* colmax, int) {
+  GJ_REQUIRE(k >= 1 && k <= kMaxRhs, "batch_rhs: 1 <= k <= 64 columns");
+  GJ_REQUIRE(n >= 1 && nb >= 0, "batch_rhs: n >= 1, nb >= 0");
+  g_last_batch_kernel = "host";
+  parallel_for(nb, nthreads_, [&](int64_t b) {
+    const double* Vb = V + b * stride_v;
+    const double* Cb = C_in ? C_in + b * stride_c : nullptr;
+    double* Yb = Y + b * stride_y;
+    for (int64_t j = 0; j < k; ++j) {
+      if (active && active[b * k + j] == 0) continue;
+      double mx = 0.0;
+      for (int64_t r = 0; r < n; ++r) {
+        double acc = 0.0;  // fp64 for both dtypes
+        for (int64_t c = 0; c < n; ++c)
+          acc += (dt == DType::F64 ? tp<double>(M)[b * stride_m + r * ldm + c]
+                                   : (double)tp<float>(M)[b * stride_m + r * ldm + c]) *
+                 Vb[c * ldv + j];
+        const double y = (Cb ? Cb[r * ldc + j] : 0.0) + sign * acc;
+        Yb[r * ldy + j] = y;
+        mx = max_keep_nan(mx, std::fabs(y));
+      }
+      if (colmax) colmax[b * k + j] = mx;
+    }
+  });
+}
+
 }  // namespace gj

@@ -968,4 +968,57 @@ void RaceCheckDevice::scale_pow2(DType dt, void* X, int64_t ldx, const Layout& L
   inner_->scale_pow2(dt, X, ldx, L, rexp_nat, cexp, s);
 }
 
+// The stack ops: one exact n x n (or n x k) region per matrix.
+void RaceCheckDevice::batch_pack(DType dt, const double* A64, int64_t stride_a, int64_t lda, int64_t n, int64_t m,
+                                 int64_t nb, void* Lt, int64_t ldl, double* norm, int32_t* exp, int s) {
+  std::vector<Acc> a;
+  if (n >= 1 && m >= n && nb > 0 && lda >= n && ldl >= nb * m) {  // (the inner device refuses anything else)
+    for (int64_t b = 0; b < nb; ++b) a.push_back(R(rect(A64 + b * stride_a, lda, n, n, 8), "A"));
+    a.push_back(W(rect(Lt, ldl, nb * m, m, (int64_t)dtype_size(dt)), "Lt"));
+    a.push_back(W(span(norm, 8 * nb), "norm"));
+    a.push_back(W(span(exp, 4 * nb), "exp"));
+  }
+  check(s, "batch_pack", a);
+  inner_->batch_pack(dt, A64, stride_a, lda, n, m, nb, Lt, ldl, norm, exp, s);
+}
+void RaceCheckDevice::batch_unpack(DType dt, const void* inv_t, int64_t n, int64_t m, int64_t nb, const int32_t* exp,
+                                   const int32_t* valid, void* X, int64_t stride_x, int64_t ldx, int s) {
+  std::vector<Acc> a;
+  if (n >= 1 && m >= n && nb > 0 && ldx >= n) {
+    const int64_t es = (int64_t)dtype_size(dt);
+    // inv_t[b][j][i], i, j < n: n rows of n elements, m apart, per block (a superset for an invalid block,
+    // whose flag is device data: it can add a report, never hide one)
+    for (int64_t b = 0; b < nb; ++b) {
+      a.push_back(R(rect(static_cast<const char*>(inv_t) + b * m * m * es, m, n, n, es), "inv_t"));
+      a.push_back(W(rect(static_cast<char*>(X) + b * stride_x * es, ldx, n, n, es), "X"));
+    }
+    a.push_back(R(span(exp, 4 * nb), "exp"));
+    a.push_back(R(span(valid, 4 * nb), "valid"));
+  }
+  check(s, "batch_unpack", a);
+  inner_->batch_unpack(dt, inv_t, n, m, nb, exp, valid, X, stride_x, ldx, s);
+}
+void RaceCheckDevice::batch_rhs(DType dt, const void* M, int64_t stride_m, int64_t ldm, int64_t n, int64_t nb,
+                                const double* V, int64_t stride_v, int64_t ldv, int64_t k, const double* C_in,
+                                int64_t stride_c, int64_t ldc, double* Y, int64_t stride_y, int64_t ldy, double sign,
+                                const int32_t* active, double* colmax, int s) {
+  std::vector<Acc> a;
+  if (k >= 1 && k <= kMaxRhs && n >= 1 && nb > 0) {
+    const int64_t es = (int64_t)dtype_size(dt);
+    // The column mask is device data that cannot be read here without waiting for the stream: every
+    // column is declared, a superset of what a masked launch touches.
+    for (int64_t b = 0; b < nb; ++b) {
+      a.push_back(R(rect(static_cast<const char*>(M) + b * stride_m * es, ldm, n, n, es), "M"));
+      a.push_back(R(rect(V + b * stride_v, ldv, k, n, 8), "V"));
+      if (C_in) a.push_back(R(rect(C_in + b * stride_c, ldc, k, n, 8), "C_in"));
+      a.push_back(W(rect(Y + b * stride_y, ldy, k, n, 8), "Y"));
+    }
+    if (active) a.push_back(R(span(active, 4 * nb * k), "active"));
+    if (colmax) a.push_back(W(span(colmax, 8 * nb * k), "colmax"));
+  }
+  check(s, "batch_rhs", a);
+  inner_->batch_rhs(dt, M, stride_m, ldm, n, nb, V, stride_v, ldv, k, C_in, stride_c, ldc, Y, stride_y, ldy, sign,
+                    active, colmax, s);
+}
+
 }  // namespace gj

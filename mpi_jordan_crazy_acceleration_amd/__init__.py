@@ -20,6 +20,7 @@ Python entry points:
 ``run(n, m, ...)``                     the CLI flow in-process (report dict)     -> models.gauss_jordan
 ``DistributedGaussJordan``             one rank per process over torch.distributed -> parallel.dist
 ``autograd``                           differentiable factor / solve / slogdet / inverse -> autograd
+``batched``                            inverse / solve / slogdet of a stack (..., n, n), n <= 1024 -> batched
 ``ops``                                kernel-level wrappers (tests, profiling)
 """
 from ._native import load_native, native_available, native_path  # noqa: F401
@@ -27,5 +28,6 @@ from .models.gauss_jordan import (Factored, GaussJordan, SingularMatrixError, co
                                  inverse, run, slogdet, solve)
 from .parallel.dist import DistributedGaussJordan  # noqa: F401
 from . import autograd  # noqa: F401,E402
+from . import batched  # noqa: F401,E402
 
 __version__ = "0.1.0"

@@ -467,3 +467,65 @@ def slogdet_batch(blocks: torch.Tensor, which: torch.Tensor = None, sign: torch.
     device_for(blocks).slogdet_batch(_DT[blocks.dtype], _p(blocks), stride, m, nb,
                                      0 if which is None else _p(which), _p(sign), _p(logabs))
     return sign, logabs
+
+
+def _stack(t: torch.Tensor, what: str):
+    """(nb, stride, ld) of a 3-D view with unit column stride; a stack of one matrix has any stride"""
+    assert t.ndim == 3 and t.stride(2) == 1, f"{what}: a 3-D view with unit column stride"
+    return int(t.shape[0]), int(t.stride(0)), int(t.stride(1))
+
+
+def batch_pack(A64: torch.Tensor, Lt: torch.Tensor, norm: torch.Tensor, exp: torch.Tensor, m: int = None):
+    """The stack's way into block_inverse (Device::batch_pack).  ``A64`` (nb, n, n) fp64, any strides with
+    unit column stride; ``Lt`` an (m, >= nb * m) view of fp64 / fp32, m = max(n, 16) by default; ``norm``
+    float64[nb], ``exp`` int32[nb].  norm[b] = ||A_b||_inf (NaN kept), exp[b] the power of two that brings it
+    into [1, 2), Lt[c, b * m + r] = -ldexp(A_b[r, c], exp[b]) in Lt's dtype, with -I below order m."""
+    nb, sa, lda = _stack(A64, "A64")
+    n = int(A64.shape[1])
+    assert A64.dtype == torch.float64 and A64.shape[2] == n
+    m = max(n, 16) if m is None else int(m)
+    assert Lt.ndim == 2 and Lt.stride(1) == 1 and Lt.shape[0] >= m and Lt.shape[1] >= nb * m
+    assert norm.dtype == torch.float64 and norm.is_contiguous() and norm.numel() >= nb
+    assert exp.dtype == torch.int32 and exp.is_contiguous() and exp.numel() >= nb
+    device_for(Lt).batch_pack(_DT[Lt.dtype], _p(A64), sa, lda, n, m, nb, _p(Lt), Lt.stride(0), _p(norm), _p(exp))
+    return Lt
+
+
+def batch_unpack(inv_t: torch.Tensor, exp: torch.Tensor, valid: torch.Tensor, X: torch.Tensor) -> torch.Tensor:
+    """block_inverse's output as inverses of the unscaled stack (Device::batch_unpack).  ``inv_t`` (nb, m, m)
+    contiguous, inv_t[b] = inv(As_b)^T; ``X`` (nb, n, n) of the same dtype, n <= m, any strides with unit
+    column stride: X[b, i, j] = ldexp(inv_t[b, j, i], exp[b]), NaN where valid[b] == 0."""
+    nb, sx, ldx = _stack(X, "X")
+    n, m = int(X.shape[1]), int(inv_t.shape[1])
+    assert inv_t.is_contiguous() and inv_t.shape == (nb, m, m) and inv_t.dtype == X.dtype and X.shape[2] == n
+    assert exp.dtype == valid.dtype == torch.int32 and exp.is_contiguous() and valid.is_contiguous()
+    device_for(X).batch_unpack(_DT[X.dtype], _p(inv_t), n, m, nb, _p(exp), _p(valid), _p(X), sx, ldx)
+    return X
+
+
+def batch_rhs(M: torch.Tensor, V: torch.Tensor, Y: torch.Tensor, C_in: torch.Tensor = None, sign: float = 1.0,
+              active: torch.Tensor = None, colmax: torch.Tensor = None, device=None) -> torch.Tensor:
+    """Y[b] = C_in[b] + sign * M[b] @ V[b] for a stack (Device::batch_rhs), in fp64 whatever M's dtype is.
+    ``M`` (nb, n, n) fp64 / fp32, ``V`` / ``Y`` / ``C_in`` (nb, n, k) fp64 with 1 <= k <= 64 (else an
+    error), all 3-D views with unit column stride; ``C_in`` None (0) or Y itself; ``active`` int32 (nb, k)
+    or None: a column with 0 is neither read nor written; ``colmax`` float64 (nb, k) or None: max |Y| per
+    (matrix, column), NaN kept, untouched for an inactive column.  ``device`` as in panel_abs_rhs."""
+    nb, sm, ldm = _stack(M, "M")
+    n, k = int(M.shape[1]), int(Y.shape[2])
+    assert V.dtype == Y.dtype == torch.float64 and M.shape[2] == n
+    assert V.shape == (nb, n, k) and Y.shape == (nb, n, k)
+    _, sv, ldv = _stack(V, "V")
+    _, sy, ldy = _stack(Y, "Y")
+    cp, sc, ldc = 0, 0, 0
+    if C_in is not None:
+        assert C_in.dtype == torch.float64 and C_in.shape == Y.shape
+        _, sc, ldc = _stack(C_in, "C_in")
+        cp = _p(C_in)
+    if active is not None:
+        assert active.dtype == torch.int32 and active.is_contiguous() and active.numel() == nb * k
+    if colmax is not None:
+        assert colmax.dtype == torch.float64 and colmax.is_contiguous() and colmax.numel() == nb * k
+    (device or device_for(Y)).batch_rhs(_DT[M.dtype], _p(M), sm, ldm, n, nb, _p(V), sv, ldv, k, cp, sc, ldc, _p(Y), sy,
+                                        ldy, float(sign), 0 if active is None else _p(active),
+                                        0 if colmax is None else _p(colmax))
+    return Y
